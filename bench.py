@@ -13,6 +13,12 @@ Launch:
       --master-addr 127.0.0.1 bench.py --gpus N ...       (one rank per GPU, RCCL)
 
 Rank 0 prints exactly one JSON line per the driver contract.
+
+A plain run does only what that line needs: set up, warm up, time --steps
+steps.  ``--dump-outputs DIR`` additionally writes what the last timed step
+computed as DIR/<name>.npy (same arguments -> same seeded inputs, so two
+builds can be compared output for output).  ``--full`` is where measurements
+beyond the headline figure belong; none exist yet.
 """
 
 import argparse
@@ -58,6 +64,50 @@ MODES = (12, 12, 12, 8)
 NUM_BLOCKS = 4
 
 
+# --dump-outputs budget (float32 elements): the prediction gets 48 MB, the
+# parameter sample 8 MB, so one rank's files stay well under 64 MB
+DUMP_Y_MAX = 12 * 2**20
+DUMP_PARAMS_MAX = 2 * 2**20
+DUMP_SEED = 20240229
+
+
+def _sample_f32(t, k, rng):
+    """Flat float32 numpy copy of ``t`` (complex as re/im pairs); tensors
+    over ``k`` elements are cut to a seeded sample of k of them, in index
+    order."""
+    t = t.detach()
+    if t.is_complex():
+        t = torch.view_as_real(t)
+    flat = t.reshape(-1)
+    if flat.numel() > k:
+        idx = rng.integers(0, flat.numel(), size=k)
+        idx.sort()
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(out_dir, y, loss, model, rank, world):
+    """Write the last timed step's results as <out_dir>/<name>.npy (float32):
+    ``loss``, ``y`` (this rank's shard of the prediction) and ``params``, a
+    fixed seeded sample of every parameter after the step's Adam update, in
+    ``model.parameters()`` order.  Ranks > 0 of a distributed run add a
+    ``.rank<r>`` suffix to the name."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    suffix = f".rank{rank}" if world > 1 and rank > 0 else ""
+    params = [q for q in model.parameters() if q.numel()]
+    per = max(1, DUMP_PARAMS_MAX // max(len(params), 1))
+    arrays = {
+        "loss": loss.reshape(1).to(torch.float32).cpu().numpy(),
+        "y": _sample_f32(y, DUMP_Y_MAX, rng),
+        "params": np.concatenate([_sample_f32(q, per, rng) for q in params]),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -82,7 +132,19 @@ def main():
                    help="explicit 6-dim partition shape (overrides presets)")
     p.add_argument("--allow-fallback", action="store_true",
                    help="skip the all-ops-native assertion (debug only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, prediction, a seeded sample of "
+                        "the updated parameters) as DIR/<name>.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements and checks beyond the "
+                        "headline figure; a plain run sets up, warms up, "
+                        "times --steps steps and prints the result line "
+                        "(nothing else is measured at present, so --full "
+                        "adds no work yet)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
 
     n = args.gpus
     assert n in PARTITIONS, f"--gpus must be one of {sorted(PARTITIONS)}"
@@ -126,12 +188,17 @@ def main():
     x = torch.rand(*info_x["shape"], device=device, dtype=dtype)
     y_true = torch.rand(*info_y["shape"], device=device, dtype=dtype)
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         optimizer.zero_grad(set_to_none=True)
         y = model(x)
         loss = criterion(y, y_true)
         loss.backward()
         optimizer.step()
+        if keep:
+            # --dump-outputs: hold on to what this step handed back
+            last["y"], last["loss"] = y.detach(), loss.detach()
         return loss
 
     dt_comm_acc = 0.0
@@ -153,8 +220,9 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.time()
-    for _ in range(args.steps):
-        step()
+    dump_at = args.steps - 1 if args.dump_outputs else -1
+    for i in range(args.steps):
+        step(keep=(i == dump_at))
         dt_comm_acc += model.dt_comm
     if use_cuda:
         torch.cuda.synchronize()
@@ -169,6 +237,10 @@ def main():
     # max over ranks
     elapsed = P_x.allreduce_scalar(elapsed, op="max")
     sec_per_batch = elapsed / args.steps
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["y"], last["loss"], model,
+                     max(P_x.rank, 0), n)
 
     if max(P_x.rank, 0) == 0:
         print(json.dumps({

@@ -652,9 +652,9 @@ __global__ __launch_bounds__(kBlock) void dft_r2c_glds_kernel(
   const int tilef = kBlock * N;                      // elements per tile
   // the counted s_waitcnt needs a compile-time-exact per-wave instruction
   // count: host picks NG = ceil(N/4) rounded up to a supported value and
-  // issues are padded to exactly NG glds (pad slots re-stage the tile's
-  // last 16 bytes; a whole-wave all-lanes-same-address pad instruction is
-  // NOT free, so NG tracks N instead of a single worst case)
+  // issues are padded to exactly NG glds (a pad instruction re-stages the
+  // tile's last 1 KiB; it is NOT free, so NG tracks N instead of a single
+  // worst case)
   const int wave = (int)(threadIdx.x / 64), lane = (int)(threadIdx.x % 64);
   const long nfl = lines * N;
   long ntiles = (lines + kBlock - 1) / kBlock;
@@ -665,8 +665,15 @@ __global__ __launch_bounds__(kBlock) void dft_r2c_glds_kernel(
     TI* dst = ring + (long)buf * tilef;
 #pragma unroll
     for (int k = 0; k < NG; ++k) {
-      long fo = (long)(wave * 64 + k * kBlock + lane) * EPV;
-      if (fo + EPV > tilef) fo = tilef - EPV;        // pad: clamp in-tile
+      // the DMA's LDS destination is wave-uniform base + lane*16, never a
+      // per-lane address: a pad wave-instruction must keep its whole 1 KiB
+      // image inside the tile, so it re-stages the tile's LAST 1 KiB
+      // (same bytes the real slots write).  Clamping every lane to the last
+      // 16 bytes instead spills 1008 bytes past the tile into the other
+      // ring buffer while it is being consumed.
+      long s0 = (long)(wave * 64 + k * kBlock) * EPV;
+      if (s0 + 64 * EPV > tilef) s0 = tilef - 64 * EPV;   // pad: stay in-tile
+      long fo = s0 + (long)lane * EPV;
       long gfo = base + fo;
       if (gfo + EPV > nfl) gfo = nfl - EPV;          // clamp last tile
       __builtin_amdgcn_global_load_lds(

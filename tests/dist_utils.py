@@ -5,7 +5,22 @@ import os
 import tempfile
 import traceback
 
+import torch
 import torch.multiprocessing as mp
+
+
+def launch_env(repo, nproc=1):
+    """Environment for a subprocess (torchrun when nproc > 1) that runs one of
+    the repo's scripts.  RCCL needs one GPU per rank, so on a machine that
+    has GPUs but fewer than ``nproc`` the ranks are given none and the world
+    runs on CPU over gloo, exactly as on a machine without a GPU."""
+    env = dict(os.environ)
+    env["PYTHONPATH"] = str(repo)
+    env.pop("WORLD_SIZE", None)
+    if nproc > 1 and torch.cuda.is_available() and torch.cuda.device_count() < nproc:
+        env["HIP_VISIBLE_DEVICES"] = ""
+        env["CUDA_VISIBLE_DEVICES"] = ""
+    return env
 
 
 def _worker(rank, world_size, fn, init_file, err_dir, args):

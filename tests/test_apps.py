@@ -11,15 +11,13 @@ import numpy as np
 import pytest
 import torch
 
-from dist_utils import run_dist
+from dist_utils import launch_env, run_dist
 
 REPO = Path(__file__).resolve().parent.parent
 
 
 def run_script(args, cwd, nproc=1, timeout=600):
-    env = dict(os.environ)
-    env["PYTHONPATH"] = str(REPO)
-    env.pop("WORLD_SIZE", None)
+    env = launch_env(REPO, nproc)
     if nproc > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",

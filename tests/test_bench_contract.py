@@ -6,7 +6,13 @@ import subprocess
 import sys
 from pathlib import Path
 
+from dist_utils import launch_env
+
 REPO = Path(__file__).resolve().parent.parent
+
+
+def _rank_env(n):
+    return launch_env(REPO, n)
 
 
 def test_bench_json_contract():
@@ -35,12 +41,40 @@ def test_bench_json_contract():
         assert k in d["config"]
 
 
-def test_bench_json_contract_4rank():
-    # the driver launches N>1 exactly like this (torchrun, one rank per GPU);
-    # on CPU the world runs over gloo with the same (1,1,2,2,1,1) partition
+def test_bench_dump_outputs_and_full(tmp_path):
+    # --dump-outputs writes the last timed step's results as float32 .npy
+    # (<= 64 MB in all); --full is accepted and keeps the result line intact
+    import numpy as np
+
     env = dict(os.environ)
     env["PYTHONPATH"] = str(REPO)
     env.pop("WORLD_SIZE", None)
+    out = tmp_path / "dump"
+    r = subprocess.run(
+        [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "2",
+         "--warmup", "0", "--width", "4", "--num-blocks", "1", "--full",
+         "--dump-outputs", str(out)],
+        capture_output=True, text=True, timeout=900, env=env, cwd=str(REPO))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "sec/batch" and d["steps"] == 2
+    assert abs(d["ms_per_step"] - d["value"] * 1e3) < 1e-6
+    files = sorted(f.name for f in out.iterdir())
+    assert files == ["loss.npy", "params.npy", "y.npy"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 2**20
+    arrs = {f.stem: np.load(f) for f in out.iterdir()}
+    for name, a in arrs.items():
+        assert a.dtype == np.float32, name
+        assert np.isfinite(a).all(), name
+    assert arrs["loss"].shape == (1,) and arrs["loss"][0] > 0
+    assert arrs["y"].size == 64 * 64 * 64 * 30
+    assert arrs["params"].size > 0 and arrs["params"].std() > 0
+
+
+def test_bench_json_contract_4rank():
+    # the driver launches N>1 exactly like this (torchrun, one rank per GPU);
+    # on CPU the world runs over gloo with the same (1,1,2,2,1,1) partition
+    env = _rank_env(4)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node=4", "--master-addr", "127.0.0.1",
@@ -57,9 +91,7 @@ def test_bench_json_contract_4rank():
 
 def test_bench_json_contract_8rank_driver_partition():
     # the exact launch+partition the driver's 8-GPU SCALE run uses
-    env = dict(os.environ)
-    env["PYTHONPATH"] = str(REPO)
-    env.pop("WORLD_SIZE", None)
+    env = _rank_env(8)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node=8", "--master-addr", "127.0.0.1",
@@ -75,9 +107,7 @@ def test_bench_json_contract_8rank_driver_partition():
 
 def test_bench_json_contract_8rank_heavy_comm():
     # trailing-axis partition: real R1/R4 all-to-alls + chunk pipeline at 8 ranks
-    env = dict(os.environ)
-    env["PYTHONPATH"] = str(REPO)
-    env.pop("WORLD_SIZE", None)
+    env = _rank_env(8)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node=8", "--master-addr", "127.0.0.1",

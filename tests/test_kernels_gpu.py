@@ -397,6 +397,30 @@ def test_dft_rfft_trunc_bigN(dtype, tt, shape, dim, m):
         f"bwd {(x.grad-xr.grad).abs().max()}"
 
 
+@pytest.mark.parametrize("N", [30, 20])   # compile-time-N and runtime-N kernels
+def test_dft_rfft_trunc_many_tiles_per_block(N):
+    # The fp32 r2c kernel runs a grid of at most 4096 blocks over 256-line
+    # tiles with a two-buffer LDS ring.  Only from the third tile of a block
+    # on is a tile staged into buffer 0 while buffer 1 is consumed, and at
+    # these N the last staging instruction of a tile is a pad: it must stay
+    # inside its own buffer.  3 * 4096 tiles give every block three tiles.
+    # Needs this size: no smaller one reaches the ring's second lap.
+    from dfno_amd.ops.fft import rfft_trunc, _t_rfft_trunc
+    torch.manual_seed(41)
+    m = 8
+    x = torch.rand(3 * 4096 * 256, N, device="cuda")
+    with torch.no_grad():
+        y1 = rfft_trunc(x, 1, m)
+        y2 = rfft_trunc(x, 1, m)
+        yr = _t_rfft_trunc(x, 1, m)
+    # same input, same kernel, no atomics: bitwise reproducible
+    assert torch.equal(torch.view_as_real(y1), torch.view_as_real(y2))
+    # a naive fp32 DFT of N terms in [0, 1): |err| <~ N * eps * sum|x| =
+    # 30 * 6e-8 * 30 = 5.4e-5; a line read from a clobbered tile is off by O(1)
+    err = (y1 - yr).abs().max().item()
+    assert err < 1e-4, f"fwd {err}"
+
+
 @pytest.mark.parametrize("dtype,tt", [(torch.complex64, 8e-4), (torch.complex128, 1e-10)])
 @pytest.mark.parametrize("shape,dim,mlo,mhi", [
     ((1, 4, 128, 16, 8), 2, 8, 8),       # radix-8x16 (128^2 weak-scaling x-dim)
