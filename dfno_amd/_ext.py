@@ -34,6 +34,7 @@ SOURCES = [
     _CSRC / "bf16.hip",
     _CSRC / "dft2d.hip",
     _CSRC / "mix_bwd.hip",
+    _CSRC / "epilogue.hip",
 ]
 
 

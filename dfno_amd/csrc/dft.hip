@@ -1018,6 +1018,11 @@ static at::Tensor twiddle_table(int N, int m, bool analysis,
 
 }  // namespace
 
+at::Tensor dfno_twiddle_table(int N, int m, bool analysis,
+                              const at::TensorOptions& opt) {
+  return twiddle_table(N, m, analysis, opt);
+}
+
 at::Tensor dft_c2c(const at::Tensor& x, int64_t dim, int64_t n,
                    int64_t m_lo, int64_t m_hi, bool analysis, double scale) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "dft_c2c: contiguous GPU input");

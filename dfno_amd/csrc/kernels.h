@@ -27,6 +27,19 @@ at::Tensor channel_mix_fwd_t(const at::Tensor& gz, const at::Tensor& W);
 std::vector<at::Tensor> linear_res_gelu_fwd(const at::Tensor& x, const at::Tensor& W,
                                             const at::Tensor& res);
 
+// fused block epilogue with the time-axis irfft synthesized on the fly
+// (epilogue.hip): z = W @ x + pad_irfft(Yt, n_out), y = gelu(z), with
+// x [B,I,S] fp32, Yt [B,O,L,m] complex64, S = L * n_out.  Returns {y, z};
+// z is empty (and never written) unless need_z.
+std::vector<at::Tensor> irfft_linear_res_gelu_fwd(const at::Tensor& x,
+                                                  const at::Tensor& W,
+                                                  const at::Tensor& Yt,
+                                                  int64_t n_out, bool need_z);
+
+// the cached host-built [N, m, 2] DFT twiddle table of dft.hip
+at::Tensor dfno_twiddle_table(int N, int m, bool analysis,
+                              const at::TensorOptions& opt);
+
 at::Tensor gelu_fwd(const at::Tensor& x);
 at::Tensor gelu_bwd(const at::Tensor& gy, const at::Tensor& z);
 std::vector<at::Tensor> add_gelu_fwd(const at::Tensor& a, const at::Tensor& b);

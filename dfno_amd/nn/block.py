@@ -33,6 +33,7 @@ from ..comm import (Repartition, _get_plan, repartition_complete,
                     repartition_issue)
 from ..partition import Partition, compute_distribution_info
 from ..ops import spectral_conv, add_gelu, linear_res_gelu, rfft_trunc, fft_trunc, pad_ifft, pad_irfft
+from ..ops import irfft_linear_res_gelu, fused_epilogue_enabled, fused_epilogue_ok
 from ..timing import comm_region
 from .linear import BroadcastedLinear
 
@@ -255,11 +256,21 @@ class DistributedFNOBlock(nn.Module):
                          self.restrict_suffixes.get(dim, 0))
         return y
 
-    def _inv_m(self, y: torch.Tensor, saved: Dict[int, int]) -> torch.Tensor:
+    def _inv_m(self, y: torch.Tensor, saved: Dict[int, int],
+               defer_irfft: bool = False) -> torch.Tensor:
+        """Inverse transforms along the trailing dims.  ``defer_irfft``
+        stops before the final time-axis ``pad_irfft`` and returns the
+        kept-mode time spectrum (the fused epilogue synthesizes it)."""
         if y.numel() == 0:
             return torch.empty(0, dtype=self.dtype, device=y.device,
                                requires_grad=torch.is_grad_enabled())
         outermost = self.dim_m[-1]
+        if defer_irfft:
+            for dim in self.dim_m[:-1]:
+                y = pad_ifft(y, dim, saved[dim],
+                             self.restrict_prefixes[dim],
+                             self.restrict_suffixes.get(dim, 0))
+            return y
         if len(self.dim_m) == 2 and y.is_cuda and y.dtype == torch.complex64:
             from ..ops.fft import zt_enabled, zt_inv
             z_dim = self.dim_m[0]
@@ -305,6 +316,28 @@ class DistributedFNOBlock(nn.Module):
         self._nch = max(1, nch)
         return self._nch
 
+    # ---- fused irfft epilogue policy ---------------------------------------
+    def _fuse_epilogue(self) -> bool:
+        """Whether the final time-axis irfft runs inside the block epilogue
+        (ops/epilogue.py) instead of materializing the real activation.
+
+        Needs R4 to be an identity (the spectrum is already laid out like
+        the block output) and the fp32 kernel range; like the chunk policy
+        it reads GLOBAL configuration only, so every rank agrees.
+        DFNO_FUSED_EPILOGUE=0 restores the two-kernel path.
+        """
+        if not fused_epilogue_enabled():
+            return False
+        T = self.in_shape[-1]
+        m = min(self.restrict_prefixes[self.dim_m[-1]], T // 2 + 1)
+        if not fused_epilogue_ok(self.dtype, self.width, self.width, T, m):
+            return False
+        if len(self.dim_m) == 2:
+            from ..ops.fft import zt_enabled
+            if zt_enabled():        # fused (z,t) synthesis owns the irfft
+                return False
+        return _get_plan(self.P_m, self.P_x, tuple(self.in_shape)).is_identity
+
     def _chunk_sizes(self, nch: int):
         w = self.width
         base, rem = divmod(w, nch)
@@ -337,14 +370,23 @@ class DistributedFNOBlock(nn.Module):
         if nch > 1:
             y = self._forward_pipelined(x, nch)
         else:
-            y, x_in = self._forward_seq(x)
+            y, x_in, spectrum = self._forward_seq(x)
+            if spectrum:
+                # y is the kept-mode time spectrum: irfft fused into the
+                # epilogue, the real chain output never reaches HBM
+                T = self.in_shape[-1]
+                return irfft_linear_res_gelu(
+                    x_in, W_res, y, T // 2 + 1, T,
+                    self.restrict_prefixes[self.dim_m[-1]])
 
         return linear_res_gelu(x_in, W_res, y)
 
     def _forward_seq(self, x: torch.Tensor):
-        """Returns (chain output, epilogue input).  The epilogue input is
-        either ``x`` itself or its StashGradFn alias when the residual
-        input-gradient fuses into the rfft adjoint (ops/fft.py stash)."""
+        """Returns (chain output, epilogue input, spectrum flag).  The
+        epilogue input is either ``x`` itself or its StashGradFn alias when
+        the residual input-gradient fuses into the rfft adjoint (ops/fft.py
+        stash).  With the flag set the chain output is still the kept-mode
+        time spectrum (see ``_fuse_epilogue``)."""
         from ..ops.fft import (StashGradFn, new_stash_key, rfft_trunc_stash,
                                stash_fusable)
 
@@ -409,12 +451,16 @@ class DistributedFNOBlock(nn.Module):
             y = self.R3(y)
         self.dt_comm += r.host_dt
 
-        y = self._inv_m(y, saved)
+        defer = (y.is_cuda and y.numel() > 0 and y.dtype == torch.complex64
+                 and self._fuse_epilogue())
+        y = self._inv_m(y, saved, defer_irfft=defer)
+        if defer:
+            return y, x_epi, True       # R4 is an identity on this path
 
         with comm_region() as r:
             y = self.R4(y)
         self.dt_comm += r.host_dt
-        return y, x_epi
+        return y, x_epi, False
 
     def _forward_pipelined(self, x: torch.Tensor, nch: int) -> torch.Tensor:
         """Channel-chunked software pipeline over the pencil chain.
