@@ -87,6 +87,14 @@ def main():
     dt = bench(lambda: ext.channel_mix_bwd_fused(gymix, zmix, x, Wmix,
                                                  False, True))
     report("channel_mix_bwd_fused (+gz out)", dt, (3 * 20 + 2 * 20) * S * 4)
+    # grad-x deferred to the rfft adjoint: no phase A, no gx store
+    dt = bench(lambda: ext.channel_mix_bwd_fused(gymix, zmix, x, Wmix,
+                                                 False, True, False))
+    report("channel_mix_bwd_fused (gz out, no gx)", dt, (3 * 20 + 20) * S * 4)
+    # the adjoint that takes it over: W^T gz + rfft_trunc_adj(G), T=30 m=8
+    Gadj = torch.randn(1, 20, S // 30, 8, device=dev, dtype=torch.complex64)
+    dt = bench(lambda: ext.rfft_adj_mix(gymix, Wmix, Gadj, 30))
+    report("rfft_adj_mix", dt, (2 * 20 * S + 20 * (S // 30) * 16) * 4)
 
     # add gelu
     a = torch.randn(1, 20, S, device=dev)

@@ -15,6 +15,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused y = gelu(W @ x + res): returns (y, z)");
   m.def("irfft_linear_res_gelu_fwd", &irfft_linear_res_gelu_fwd,
         "fused y = gelu(W @ x + pad_irfft(Yt)): returns (y, z)");
+  m.def("rfft_adj_mix", &rfft_adj_mix,
+        "fused gx = W^T @ gz + rfft_trunc_adj(G, n)");
   m.def("gelu_fwd", &gelu_fwd, "exact gelu");
   m.def("gelu_bwd", &gelu_bwd, "gelu backward (gy, z) -> gz");
   m.def("add_gelu_fwd", &add_gelu_fwd, "fused residual add + gelu: returns (y, z)");
@@ -22,7 +24,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("proj_head_bwd", &proj_head_bwd,
         "fused head backward: returns (gz3, gb3, gW4, gb4)");
   m.def("channel_mix_bwd_fused", &channel_mix_bwd_fused,
-        "fused trunk mix backward: (gx, gW, gb, gz)");
+        "fused trunk mix backward: (gx, gW, gb, gz)",
+        py::arg("gy"), py::arg("z"), py::arg("x"), py::arg("W"),
+        py::arg("want_bias"), py::arg("want_gz"), py::arg("want_gx") = true);
   m.def("proj_head_bwd_fused", &proj_head_bwd_fused,
         "fully-fused flagship head backward: (gx, gW3, gb3, gW4, gb4)");
   m.def("lift_head_fwd", &lift_head_fwd, "fused time-lift + channel-lift + gelus");

@@ -36,7 +36,13 @@ constexpr int kBlock = 256;
 
 // IT/OT/NT/MT > 0 pin I, O, N, m at compile time (full unroll, register
 // twiddles, float4 LDS reads); 0 = runtime extents, scalar accesses.
-template <int IMAX, int VEC, int IT, int OT, int NT, int MT>
+//
+// ADJ selects the adjoint mode (rfft_adj_mix below): the register-resident
+// columns are gz, W is staged TRANSPOSED, the spectrum is the rfft adjoint's
+// input (unit scale, no interior doubling, DC / Nyquist imaginary parts
+// kept — dft_c2r_last_kernel with factors=false), and the single output is
+// the plain sum: no GELU, no second store.
+template <int IMAX, int VEC, int IT, int OT, int NT, int MT, bool ADJ = false>
 __global__ __launch_bounds__(kBlock) void irfft_mix_gelu_kernel(
     const float* __restrict__ x, const float* __restrict__ W,
     const float* __restrict__ Yt, const float* __restrict__ tw,
@@ -56,7 +62,15 @@ __global__ __launch_bounds__(kBlock) void irfft_mix_gelu_kernel(
   float* twl = Wl + (((size_t)O * I + 3) & ~(size_t)3);    // [N*m*2] (!PIN)
   float* Yl = twl + (PIN ? 0 : (((size_t)N * M2 + 3) & ~(size_t)3));
                                                            // [O][LT][2m]
-  for (int k = threadIdx.x; k < O * I; k += kBlock) Wl[k] = W[k];
+  if constexpr (ADJ) {
+    // W is [I, O] in this kernel's roles (the mix's [O, I]): Wl = W^T
+    for (int k = threadIdx.x; k < O * I; k += kBlock) {
+      const int o = k / I;
+      Wl[k] = W[(size_t)(k - o * I) * O + o];
+    }
+  } else {
+    for (int k = threadIdx.x; k < O * I; k += kBlock) Wl[k] = W[k];
+  }
   if constexpr (!PIN)
     for (int k = threadIdx.x; k < N * M2; k += kBlock) twl[k] = tw[k];
 
@@ -88,33 +102,39 @@ __global__ __launch_bounds__(kBlock) void irfft_mix_gelu_kernel(
     __syncthreads();                    // last tile's readers are done
     // stage the tile's spectrum lines: per channel one contiguous run of
     // nl*2m floats, scaled as dft_c2r_last_kernel scales its registers
-    // (interior modes doubled, imaginary part of DC / Nyquist dropped)
+    // (interior modes doubled, imaginary part of DC / Nyquist dropped;
+    // ADJ: copied as they are, its factors=false)
     const int run = nl * M2;
     if constexpr (PIN) {
       const int run4 = run / 4;         // MT even: float4 = modes (k, k+1)
       for (int idx = threadIdx.x; idx < O * run4; idx += kBlock) {
         const int o = idx / run4;
         const int r4 = idx - o * run4;
-        const int k = (r4 * 2) % MT;
         float4 v = *reinterpret_cast<const float4*>(
             Yt + (((long)b * O + o) * L + l0) * M2 + (long)r4 * 4);
-        const bool e0 = (k == 0) || (2 * k == NT);
-        const bool e1 = (2 * (k + 1) == NT);
-        const float f0 = e0 ? scale : 2.0f * scale;
-        const float f1 = e1 ? scale : 2.0f * scale;
-        v.x = f0 * v.x; v.y = e0 ? 0.0f : f0 * v.y;
-        v.z = f1 * v.z; v.w = e1 ? 0.0f : f1 * v.w;
+        if constexpr (!ADJ) {
+          const int k = (r4 * 2) % MT;
+          const bool e0 = (k == 0) || (2 * k == NT);
+          const bool e1 = (2 * (k + 1) == NT);
+          const float f0 = e0 ? scale : 2.0f * scale;
+          const float f1 = e1 ? scale : 2.0f * scale;
+          v.x = f0 * v.x; v.y = e0 ? 0.0f : f0 * v.y;
+          v.z = f1 * v.z; v.w = e1 ? 0.0f : f1 * v.w;
+        }
         *reinterpret_cast<float4*>(Yl + (size_t)o * LT * M2 + (size_t)r4 * 4) = v;
       }
     } else {
       for (int idx = threadIdx.x; idx < O * run; idx += kBlock) {
         const int o = idx / run;
         const int r = idx - o * run;
-        const int k = (r >> 1) % m;
-        const bool edge = (k == 0) || (2 * k == N);
-        const float f = edge ? scale : 2.0f * scale;
-        float v = f * Yt[(((long)b * O + o) * L + l0) * M2 + r];
-        if (edge && (r & 1)) v = 0.0f;
+        float v = Yt[(((long)b * O + o) * L + l0) * M2 + r];
+        if constexpr (!ADJ) {
+          const int k = (r >> 1) % m;
+          const bool edge = (k == 0) || (2 * k == N);
+          const float f = edge ? scale : 2.0f * scale;
+          v = f * v;
+          if (edge && (r & 1)) v = 0.0f;
+        }
         Yl[(size_t)o * LT * M2 + r] = v;
       }
     }
@@ -182,7 +202,15 @@ __global__ __launch_bounds__(kBlock) void irfft_mix_gelu_kernel(
       }
 #pragma unroll
       for (int v = 0; v < VEC; ++v) acc[v] += syn[v];
-      if constexpr (VEC == 2) {
+      if constexpr (ADJ) {
+        if constexpr (VEC == 2) {
+          *reinterpret_cast<float2*>(yb + (long)o * S) =
+              make_float2(acc[0], acc[1]);
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) yb[(long)o * S + v] = acc[v];
+        }
+      } else if constexpr (VEC == 2) {
         if (write_z)
           *reinterpret_cast<float2*>(zb + (long)o * S) =
               make_float2(acc[0], acc[1]);
@@ -196,6 +224,45 @@ __global__ __launch_bounds__(kBlock) void irfft_mix_gelu_kernel(
         }
       }
     }
+  }
+}
+
+// One dispatch for both modes.  I/O are the KERNEL's roles: I register-
+// resident input channels, O output channels (= spectrum channels).
+template <bool ADJ>
+void launch_irfft_mix(const float* xp, const float* Wp, const float* Yp,
+                      const float* twp, float* yp, float* zp, int B, int I,
+                      int O, long L, int N, int m, float scale, bool write_z,
+                      hipStream_t stream) {
+  auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+  if (I == 20 && O == 20 && N == 30 && m == 8) {
+    constexpr int LT = 17;              // 17 lines x 15 float2 = 255 threads
+    const long ntiles = (long)B * ((L + LT - 1) / LT);
+    const int grid = (int)std::min(ntiles, 256L * 8);
+    const size_t smem = sizeof(float) * (pad4(400) + (size_t)20 * LT * 16);
+    hipLaunchKernelGGL((irfft_mix_gelu_kernel<20, 2, 20, 20, 30, 8, ADJ>),
+                       dim3(grid), dim3(kBlock), smem, stream, xp, Wp, Yp, twp,
+                       yp, zp, B, I, O, L, N, m, LT, scale, write_z);
+  } else {
+    // whole lines per tile, one column per thread; the spectrum tile is
+    // capped at 32 KiB so several blocks stay resident per CU
+    int LT = kBlock / N;
+    const size_t line_bytes = sizeof(float) * (size_t)O * 2 * m;
+    LT = (int)std::max<size_t>(1, std::min<size_t>(LT, (32 * 1024) / line_bytes));
+    const long ntiles = (long)B * ((L + LT - 1) / LT);
+    const int grid = (int)std::min(ntiles, 256L * 8);
+    const size_t smem = sizeof(float) * (pad4((size_t)O * I) +
+                                         pad4((size_t)N * 2 * m) +
+                                         (size_t)O * LT * 2 * m);
+#define EPI_GENERIC(CAP)                                                       \
+    hipLaunchKernelGGL((irfft_mix_gelu_kernel<CAP, 1, 0, 0, 0, 0, ADJ>),       \
+                       dim3(grid), dim3(kBlock), smem, stream, xp, Wp, Yp,     \
+                       twp, yp, zp, B, I, O, L, N, m, LT, scale, write_z);
+    if (I <= 8) { EPI_GENERIC(8) }
+    else if (I <= 16) { EPI_GENERIC(16) }
+    else if (I <= 24) { EPI_GENERIC(24) }
+    else { EPI_GENERIC(32) }
+#undef EPI_GENERIC
   }
 }
 
@@ -235,43 +302,53 @@ std::vector<at::Tensor> irfft_linear_res_gelu_fwd(const at::Tensor& x,
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   auto tw = dfno_twiddle_table(N, m, /*analysis=*/false, x.options());
   const float scale = (float)(1.0 / (double)N);
-  const float* xp = x.data_ptr<float>();
-  const float* Wp = W.data_ptr<float>();
-  const float* Yp = reinterpret_cast<const float*>(Yt.data_ptr());
-  const float* twp = tw.data_ptr<float>();
   float* yp = y.data_ptr<float>();
   float* zp = need_z ? z.data_ptr<float>() : yp;   // never stored through
-
-  auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-  if (I == 20 && O == 20 && N == 30 && m == 8) {
-    constexpr int LT = 17;              // 17 lines x 15 float2 = 255 threads
-    const long ntiles = (long)B * ((L + LT - 1) / LT);
-    const int grid = (int)std::min(ntiles, 256L * 8);
-    const size_t smem = sizeof(float) * (pad4(400) + (size_t)20 * LT * 16);
-    hipLaunchKernelGGL((irfft_mix_gelu_kernel<20, 2, 20, 20, 30, 8>),
-                       dim3(grid), dim3(kBlock), smem, stream, xp, Wp, Yp, twp,
-                       yp, zp, B, I, O, L, N, m, LT, scale, need_z);
-  } else {
-    // whole lines per tile, one column per thread; the spectrum tile is
-    // capped at 32 KiB so several blocks stay resident per CU
-    int LT = kBlock / N;
-    const size_t line_bytes = sizeof(float) * (size_t)O * 2 * m;
-    LT = (int)std::max<size_t>(1, std::min<size_t>(LT, (32 * 1024) / line_bytes));
-    const long ntiles = (long)B * ((L + LT - 1) / LT);
-    const int grid = (int)std::min(ntiles, 256L * 8);
-    const size_t smem = sizeof(float) * (pad4((size_t)O * I) +
-                                         pad4((size_t)N * 2 * m) +
-                                         (size_t)O * LT * 2 * m);
-#define EPI_GENERIC(CAP)                                                       \
-    hipLaunchKernelGGL((irfft_mix_gelu_kernel<CAP, 1, 0, 0, 0, 0>),            \
-                       dim3(grid), dim3(kBlock), smem, stream, xp, Wp, Yp,     \
-                       twp, yp, zp, B, I, O, L, N, m, LT, scale, need_z);
-    if (I <= 8) { EPI_GENERIC(8) }
-    else if (I <= 16) { EPI_GENERIC(16) }
-    else if (I <= 24) { EPI_GENERIC(24) }
-    else { EPI_GENERIC(32) }
-#undef EPI_GENERIC
-  }
+  launch_irfft_mix<false>(x.data_ptr<float>(), W.data_ptr<float>(),
+                          reinterpret_cast<const float*>(Yt.data_ptr()),
+                          tw.data_ptr<float>(), yp, zp, B, I, O, L, N, m,
+                          scale, need_z, stream);
   DFNO_CHECK_LAUNCH("irfft_linear_res_gelu");
   return {y, z};
+}
+
+at::Tensor rfft_adj_mix(const at::Tensor& gz, const at::Tensor& W,
+                        const at::Tensor& G, int64_t n) {
+  TORCH_CHECK(gz.is_cuda() && gz.is_contiguous() &&
+              gz.scalar_type() == at::kFloat,
+              "rfft_adj_mix: gz must be contiguous fp32 on GPU");
+  TORCH_CHECK(W.is_cuda() && W.is_contiguous() && W.scalar_type() == at::kFloat,
+              "rfft_adj_mix: W must be contiguous fp32 on GPU");
+  TORCH_CHECK(G.is_cuda() && G.is_contiguous() &&
+              G.scalar_type() == at::kComplexFloat,
+              "rfft_adj_mix: G must be contiguous complex64 on GPU");
+  TORCH_CHECK(gz.dim() == 3 && W.dim() == 2 && G.dim() == 4,
+              "rfft_adj_mix: gz [B,O,S], W [O,I], G [B,I,L,m]");
+  const int B = (int)gz.size(0), O = (int)gz.size(1);
+  const long S = gz.size(2);
+  const int I = (int)W.size(1);
+  const long L = G.size(2);
+  const int m = (int)G.size(3);
+  const int N = (int)n;
+  TORCH_CHECK((int)W.size(0) == O, "rfft_adj_mix: W/O mismatch");
+  TORCH_CHECK(G.size(0) == B && (int)G.size(1) == I && L * N == S,
+              "rfft_adj_mix: G shape mismatch");
+  // the roles swap against the forward mode: the mix's O channels are the
+  // register-resident ones (<= 32), its I channels the outputs (<= 64)
+  TORCH_CHECK(O >= 1 && O <= 32 && I >= 1 && I <= 64 && N >= 1 && N <= 64 &&
+              m >= 1 && m <= 32 && m <= N / 2 + 1,
+              "rfft_adj_mix: needs O<=32, I<=64, N<=64, m<=min(32,N/2+1)");
+
+  auto gx = at::empty({B, I, S}, gz.options());
+  if (gz.numel() == 0) return gx;
+
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  auto tw = dfno_twiddle_table(N, m, /*analysis=*/false, gz.options());
+  float* gp = gx.data_ptr<float>();
+  launch_irfft_mix<true>(gz.data_ptr<float>(), W.data_ptr<float>(),
+                         reinterpret_cast<const float*>(G.data_ptr()),
+                         tw.data_ptr<float>(), gp, gp, B, /*I=*/O, /*O=*/I, L,
+                         N, m, 1.0f, false, stream);
+  DFNO_CHECK_LAUNCH("rfft_adj_mix");
+  return gx;
 }

@@ -36,6 +36,13 @@ std::vector<at::Tensor> irfft_linear_res_gelu_fwd(const at::Tensor& x,
                                                   const at::Tensor& Yt,
                                                   int64_t n_out, bool need_z);
 
+// adjoint mode of the same kernel: the residual mix's grad-x folded into the
+// rfft adjoint, gx = W^T @ gz + rfft_trunc_adj(G, n), i.e.
+// channel_mix_fwd_t(gz, W) + dft_rfft_trunc_adj(G, 3, n) without the W^T gz
+// tensor in HBM.  gz [B,O,S] fp32, W [O,I], G [B,I,L,m] complex64, S = L * n.
+at::Tensor rfft_adj_mix(const at::Tensor& gz, const at::Tensor& W,
+                        const at::Tensor& G, int64_t n);
+
 // the cached host-built [N, m, 2] DFT twiddle table of dft.hip
 at::Tensor dfno_twiddle_table(int N, int m, bool analysis,
                               const at::TensorOptions& opt);
@@ -68,12 +75,15 @@ std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor
 
 // fused trunk 20x20 mix backward (mix_bwd.hip): gz = gy * gelu'(z) lives
 // only as an LDS tile; returns {gx, gW, gb, gz} (gb empty unless
-// want_bias, gz empty unless want_gz — the linear_res_gelu residual grad)
+// want_bias, gz empty unless want_gz — the linear_res_gelu residual grad;
+// gx empty and its MFMA phase compiled out unless want_gx, which needs
+// want_gz: the caller then owns gx = W^T gz, see rfft_adj_mix)
 std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
                                               const at::Tensor& z,
                                               const at::Tensor& x,
                                               const at::Tensor& W,
-                                              bool want_bias, bool want_gz);
+                                              bool want_bias, bool want_gz,
+                                              bool want_gx = true);
 
 // fused lift head (T_in == 1): y = gelu(W2 @ gelu(W1 *t x + b1) + b2)
 at::Tensor lift_head_fwd(const at::Tensor& x, const at::Tensor& W1,

@@ -41,8 +41,10 @@ __device__ __forceinline__ void mb_st(unsigned short* p, float v) {
 
 // TIO = unsigned short selects bf16 activations (fp32 compute; W and the
 // gW/gb accumulators stay fp32).  PH: phase mask for perf bisection
-// (1 staging+gz, +2 gx, +4 gW); production uses 7.
-template <typename TIO, bool WG, int PH = 7, int TS = 64>
+// (1 staging+gz, +2 gx, +4 gW); production uses 7.  WX = false compiles
+// phase A (gx = W^T gz and its store) out: the caller applies W^T to the
+// streamed-back gz itself (rfft_adj_mix, epilogue.hip); gx is never touched.
+template <typename TIO, bool WG, int PH = 7, int TS = 64, bool WX = true>
 __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
     const TIO* __restrict__ gy, const TIO* __restrict__ z,
     const TIO* __restrict__ x, const float* __restrict__ W,
@@ -116,11 +118,12 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
     }
     prefetch(t + gridDim.x);
     __syncthreads();
-    if constexpr ((PH & 2) == 0 && (PH & 4) == 0) continue;
+    constexpr bool kPhaseA = WX && (PH & 2) != 0;
+    if constexpr (!kPhaseA && (PH & 4) == 0) continue;
     // phase A: gx = W^T @ gz.  A[m=i][k=o] = W[o*C+i] (per-lane global,
     // L1-resident), B[n=c][k=o] = gzt[o][c]; K = C padded to 24.
 #pragma unroll
-    for (int pp = 0; pp < ((PH & 2) ? (2 * (TS / 16)) / 4 : 0); ++pp) {
+    for (int pp = 0; pp < (kPhaseA ? (2 * (TS / 16)) / 4 : 0); ++pp) {
       const int p = wave + 4 * pp;
       const int mt = p / (TS / 16), nt = p % (TS / 16);
       const int m = mt * 16 + l16;
@@ -185,7 +188,8 @@ std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
                                               const at::Tensor& z,
                                               const at::Tensor& x,
                                               const at::Tensor& W,
-                                              bool want_bias, bool want_gz) {
+                                              bool want_bias, bool want_gz,
+                                              bool want_gx) {
   const bool bf16 = gy.scalar_type() == at::kBFloat16;
   TORCH_CHECK(gy.is_cuda() && gy.is_contiguous() && z.is_contiguous() &&
               x.is_contiguous() && W.is_contiguous() &&
@@ -201,7 +205,11 @@ std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
   TORCH_CHECK(gy.numel() == x.numel() && z.numel() == x.numel(),
               "mix_bwd_fused: shape mismatch");
 
-  auto gx = at::empty({B, I, S}, x.options());
+  TORCH_CHECK(want_gx || want_gz,
+              "mix_bwd_fused: want_gx=false needs want_gz (grad-x is then "
+              "the caller's W^T gz)");
+  auto gx = want_gx ? at::empty({B, I, S}, x.options())
+                    : at::empty({0}, x.options());
   auto fopt = x.options().dtype(at::kFloat);   // gW/gb accumulate fp32
   auto gW = at::zeros({O, I}, fopt);
   auto gb = want_bias ? at::zeros({O}, fopt) : at::empty({0}, fopt);
@@ -234,7 +242,22 @@ std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
                      W.data_ptr<float>(),                                    \
                      reinterpret_cast<TIO*>(gx.data_ptr()),                  \
                      gW.data_ptr<float>(), gbp, GZP, B, S)
-  if (bf16) {
+  // gz + gW only: phase A is compiled out, so gx is never stored through
+#define MB_LAUNCH_NOGX(TIO, GZP)                                             \
+  hipLaunchKernelGGL((mix_bwd_fused_kernel<TIO, true, 7, 64, false>),       \
+                     dim3(grid), dim3(kBlock), smem, stream,                 \
+                     reinterpret_cast<const TIO*>(gy.data_ptr()),            \
+                     reinterpret_cast<const TIO*>(z.data_ptr()),             \
+                     reinterpret_cast<const TIO*>(x.data_ptr()),             \
+                     W.data_ptr<float>(), static_cast<TIO*>(nullptr),        \
+                     gW.data_ptr<float>(), gbp, GZP, B, S)
+  if (!want_gx) {
+    if (bf16)
+      MB_LAUNCH_NOGX(unsigned short,
+                     reinterpret_cast<unsigned short*>(gz.data_ptr()));
+    else
+      MB_LAUNCH_NOGX(float, reinterpret_cast<float*>(gz.data_ptr()));
+  } else if (bf16) {
     auto gzp = want_gz ? reinterpret_cast<unsigned short*>(gz.data_ptr())
                        : nullptr;
     if (want_gz) MB_LAUNCH(unsigned short, true, gzp);
@@ -250,6 +273,7 @@ std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
     }
     else         MB_LAUNCH(float, false, nullptr);
   }
+#undef MB_LAUNCH_NOGX
 #undef MB_LAUNCH_T
 #undef MB_LAUNCH_P
 #undef MB_LAUNCH

@@ -370,23 +370,28 @@ class DistributedFNOBlock(nn.Module):
         if nch > 1:
             y = self._forward_pipelined(x, nch)
         else:
-            y, x_in, spectrum = self._forward_seq(x)
+            y, x_in, spectrum, stash = self._forward_seq(x)
             if spectrum:
                 # y is the kept-mode time spectrum: irfft fused into the
-                # epilogue, the real chain output never reaches HBM
+                # epilogue, the real chain output never reaches HBM.  With
+                # a stash entry the epilogue routes its grad-x into the
+                # rfft adjoint itself (as (gz, W) for the fused adjoint
+                # kernel where it applies, through the alias otherwise).
                 T = self.in_shape[-1]
                 return irfft_linear_res_gelu(
                     x_in, W_res, y, T // 2 + 1, T,
-                    self.restrict_prefixes[self.dim_m[-1]])
+                    self.restrict_prefixes[self.dim_m[-1]], stash=stash)
 
         return linear_res_gelu(x_in, W_res, y)
 
     def _forward_seq(self, x: torch.Tensor):
-        """Returns (chain output, epilogue input, spectrum flag).  The
-        epilogue input is either ``x`` itself or its StashGradFn alias when
-        the residual input-gradient fuses into the rfft adjoint (ops/fft.py
-        stash).  With the flag set the chain output is still the kept-mode
-        time spectrum (see ``_fuse_epilogue``)."""
+        """Returns (chain output, epilogue input, spectrum flag, stash).
+        The epilogue input is either ``x`` itself or its StashGradFn alias
+        when the residual input-gradient fuses into the rfft adjoint
+        (ops/fft.py stash).  With the flag set the chain output is still
+        the kept-mode time spectrum (see ``_fuse_epilogue``); ``stash`` is
+        then the rfft's ``(key, token)`` where one is open and the alias
+        has NOT been made — the fused epilogue owns that choice."""
         from ..ops.fft import (StashGradFn, new_stash_key, rfft_trunc_stash,
                                stash_fusable)
 
@@ -397,6 +402,7 @@ class DistributedFNOBlock(nn.Module):
         self.dt_comm += r.host_dt
 
         x_epi = x_orig
+        stash = None
         outermost = self.dim_m[-1]
         zt_stash = False
         if (x is x_orig and len(self.dim_m) == 2 and x.is_cuda
@@ -430,7 +436,7 @@ class DistributedFNOBlock(nn.Module):
                 saved[dim] = xm.shape[dim]
                 xm = fft_trunc(xm, dim, self.restrict_prefixes[dim],
                                self.restrict_suffixes.get(dim, 0))
-            x_epi = StashGradFn.apply(x_orig, tok, key)
+            stash = (key, tok)      # alias made below, or by the epilogue
             x = xm
         else:
             x = self._fwd_m(x, saved)
@@ -455,12 +461,14 @@ class DistributedFNOBlock(nn.Module):
                  and self._fuse_epilogue())
         y = self._inv_m(y, saved, defer_irfft=defer)
         if defer:
-            return y, x_epi, True       # R4 is an identity on this path
+            return y, x_epi, True, stash    # R4 is an identity on this path
+        if stash is not None:
+            x_epi = StashGradFn.apply(x_orig, stash[1], stash[0])
 
         with comm_region() as r:
             y = self.R4(y)
         self.dt_comm += r.host_dt
-        return y, x_epi, False
+        return y, x_epi, False, None
 
     def _forward_pipelined(self, x: torch.Tensor, nch: int) -> torch.Tensor:
         """Channel-chunked software pipeline over the pencil chain.

@@ -178,6 +178,10 @@ class _PadIrfftFn(torch.autograd.Function):
 # LAST producer of the chain-side gradient.  A zero-size token from the
 # rfft forward into the stash node makes the backward ordering a hard graph
 # dependency: the stash backward must run before the rfft adjoint.
+#
+# A stash entry is either that gradient tensor or, from the fused irfft
+# epilogue, the pair (gz, W): the adjoint kernel then applies W^T itself
+# (rfft_adj_mix) and the gradient tensor never exists.
 
 import itertools as _itertools
 
@@ -225,7 +229,17 @@ class _RfftTruncStashFn(torch.autograd.Function):
             raise RuntimeError(
                 "rfft stash: epilogue gradient missing (stash backward did "
                 "not run before the rfft adjoint)")
-        if ctx.bf16:
+        if isinstance(acc, tuple):
+            # (gz, W) from the fused epilogue (ops/epilogue.py): the
+            # residual grad-x W^T gz is applied inside the adjoint kernel
+            gz, W = acc
+            G = gy.contiguous()
+            shape = list(G.shape)
+            shape[-1] = ctx.n
+            gx = ext.rfft_adj_mix(
+                gz, W, G.reshape(gz.shape[0], W.shape[1], -1, ctx.m), ctx.n)
+            gx = gx.reshape(shape)
+        elif ctx.bf16:
             gx = ext.dft_rfft_trunc_adj_bf16(gy.contiguous(), ctx.dim,
                                              ctx.n, acc)
         else:
