@@ -132,7 +132,7 @@ def main():
 
 
 if __name__ == "__main__":
-    if "--dft" not in sys.argv:
+    if "--dft" not in sys.argv and "--lift" not in sys.argv:
         main()
 
 
@@ -165,3 +165,94 @@ def dft_bench():
 
 if "__main__" == __name__ and "--dft" in sys.argv:
     dft_bench()
+
+
+def _alternate(fns, rounds=5, iters=50):
+    """Time each fn in turn, `rounds` times over; median seconds per call."""
+    times = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            times[i].append(bench(fn, iters=iters, warmup=5))
+    return [sorted(t)[len(t) // 2] for t in times]
+
+
+def lift_bench():
+    """Fused lift head vs the composed linears at the Navier-Stokes shapes
+    ([10,1,X,X,10] -> 40, width 20): per-rank X = 32 and single-GPU X = 64.
+    Both paths run on identical inputs, alternating, in this one process."""
+    from dfno_amd.ops import lift_head
+    from dfno_amd.ops.pointwise import linear_nd
+
+    B, C, Ti, To, W = 10, 1, 10, 40, 20
+    for X in (32, 64):
+        S = X * X
+        for dtype in (torch.float32, torch.bfloat16):
+            torch.manual_seed(0)
+            es = 4 if dtype == torch.float32 else 2
+            x = torch.randn(B, C, X, X, Ti, device="cuda", dtype=dtype,
+                            requires_grad=True)
+            ws = [torch.randn(To, Ti, device="cuda", dtype=dtype) / Ti,
+                  torch.randn(To, device="cuda", dtype=dtype),
+                  torch.randn(W, C, device="cuda", dtype=dtype) / C,
+                  torch.randn(W, device="cuda", dtype=dtype)]
+            ws = [w.requires_grad_(True) for w in ws]
+            gy = torch.randn(B, W, X, X, To, device="cuda", dtype=dtype)
+
+            def fused():
+                return lift_head(x, *ws)
+
+            def composed():
+                h = linear_nd(x, ws[0], ws[1], -1, "gelu")
+                return linear_nd(h, ws[2], ws[3], 1, "gelu")
+
+            def fb(f):
+                return lambda: torch.autograd.grad(f(), [x] + ws, gy)
+
+            with torch.no_grad():
+                tf, tc = _alternate([fused, composed])
+            tfb, tcb = _alternate([fb(fused), fb(composed)])
+            nin, nout = B * C * S * Ti, B * W * S * To
+            tag = f"S={X}x{X} {str(dtype).split('.')[-1]}"
+            report(f"lift fused    fwd      {tag}", tf, (nin + nout) * es)
+            report(f"lift composed fwd      {tag}", tc, (nin + nout) * es)
+            report(f"lift fused    fwd+bwd  {tag}", tfb, 2 * (nin + nout) * es + nin * es)
+            report(f"lift composed fwd+bwd  {tag}", tcb, 2 * (nin + nout) * es + nin * es)
+
+
+def lift_model_bench():
+    """fwd+bwd of the NS-shape model ([10,1,64,64,10] -> 40, width 20, 4
+    blocks, one GPU) with the fused lift on and forced off, alternating."""
+    import dfno_amd as dfno
+    import dfno_amd.ops as ops
+
+    gate = ops.lift_head_supported
+    for dtype in (torch.float32, torch.bfloat16):
+        torch.manual_seed(0)
+        _, P_x, _ = dfno.create_standard_partitions((1, 1, 1, 1, 1))
+        model = dfno.DistributedFNONd(P_x, [10, 1, 64, 64, 10], 40, 20, (4, 4, 4),
+                                      num_blocks=4, device=torch.device("cuda"),
+                                      dtype=dtype)
+        x = torch.rand(10, 1, 64, 64, 10, device="cuda", dtype=dtype)
+
+        def step(on):
+            def run():
+                ops.lift_head_supported = gate if on else (lambda *a: False)
+                try:
+                    model.zero_grad(set_to_none=True)
+                    model(x).float().square().mean().backward()
+                finally:
+                    ops.lift_head_supported = gate
+            return run
+
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            t_on, t_off = _alternate([step(True), step(False)], iters=20)
+        name = str(dtype).split(".")[-1]
+        print(f"NS model fwd+bwd {name}: fused lift {t_on*1e3:.3f} ms, "
+              f"composed lift {t_off*1e3:.3f} ms")
+
+
+if "__main__" == __name__ and "--lift" in sys.argv:
+    lift_bench()
+    lift_model_bench()

@@ -85,7 +85,9 @@ std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
                                               bool want_bias, bool want_gz,
                                               bool want_gx = true);
 
-// fused lift head (T_in == 1): y = gelu(W2 @ gelu(W1 *t x + b1) + b2)
+// fused lift head: y = gelu(W2 @ gelu(W1 @t x + b1) + b2).  x is [B,C,S]
+// (T_in == 1, T_out <= 32) or [B,C,S,Ti] (Ti <= 16, T_out <= 64); C <= 4,
+// width <= 24.  Out-of-range shapes raise.
 at::Tensor lift_head_fwd(const at::Tensor& x, const at::Tensor& W1,
                          const at::Tensor& b1, const at::Tensor& W2,
                          const at::Tensor& b2);

@@ -99,8 +99,9 @@ class DistributedFNONd(nn.Module):
 
     def _lift(self, x: torch.Tensor) -> torch.Tensor:
         """time lift T_in -> T_out then channel lift C_in -> width, each
-        with GELU.  One fused kernel on GPU when T_in == 1 (ops.lift_head);
-        the composed path otherwise."""
+        with GELU.  One fused kernel on GPU (ops.lift_head) for T_in <= 16,
+        T_out <= 64, C_in <= 4, width <= 24 in fp32/fp64/bf16; the composed
+        path (recorded as a fallback) otherwise."""
         from ..ops import lift_head, lift_head_supported
         from ..timing import comm_region
         from ..dispatch import note_fallback

@@ -1,8 +1,9 @@
 """Fused FNO lift head op (see csrc/lift_head.hip).
 
-Applies linear1 (time lift, T_in == 1) + GELU + linear2 (channel lift) +
-GELU in one kernel.  CPU / unsupported shapes use the composed path in the
-model instead.
+Applies linear1 (time lift T_in -> T_out) + GELU + linear2 (channel lift) +
+GELU in one kernel, for 1 <= T_in <= 16, T_out <= 64, C_in <= 4 and
+width <= 24.  CPU / unsupported shapes use the composed path in the model
+instead.
 """
 
 from __future__ import annotations
@@ -13,28 +14,35 @@ from .. import _ext
 
 __all__ = ["lift_head", "lift_head_supported"]
 
+# caps of the kernels (LDS tiles / register arrays are sized by them; the
+# extension re-checks every one before launching)
+MAX_T_IN, MAX_T_OUT, MAX_C_IN, MAX_WIDTH = 16, 64, 4, 24
+
 
 def lift_head_supported(x, t_in, t_out, c_in, width) -> bool:
     return (x.is_cuda
             and x.dtype in (torch.float32, torch.float64, torch.bfloat16)
-            and t_in == 1 and t_out <= 32 and c_in <= 4 and width <= 24)
+            and 1 <= t_in <= MAX_T_IN and 1 <= t_out <= MAX_T_OUT
+            and 1 <= c_in <= MAX_C_IN and 1 <= width <= MAX_WIDTH)
 
 
 class _LiftHeadFn(torch.autograd.Function):
+    """xs is [B, C, S] (T_in == 1 kernels) or [B, C, S, T_in] (general)."""
+
     @staticmethod
-    def forward(ctx, x3, W1, b1, W2, b2):
+    def forward(ctx, xs, W1, b1, W2, b2):
         ext = _ext.get(required=True)
-        out = ext.lift_head_fwd(x3, W1.contiguous(), b1.contiguous(),
+        out = ext.lift_head_fwd(xs, W1.contiguous(), b1.contiguous(),
                                 W2.contiguous(), b2.contiguous())
-        ctx.save_for_backward(x3, W1, b1, W2, b2)
+        ctx.save_for_backward(xs, W1, b1, W2, b2)
         return out
 
     @staticmethod
     def backward(ctx, gy):
-        x3, W1, b1, W2, b2 = ctx.saved_tensors
+        xs, W1, b1, W2, b2 = ctx.saved_tensors
         ext = _ext.get(required=True)
         gx, gW1, gb1, gW2, gb2 = ext.lift_head_bwd(
-            gy.contiguous(), x3, W1.contiguous(), b1.contiguous(),
+            gy.contiguous(), xs, W1.contiguous(), b1.contiguous(),
             W2.contiguous(), b2.contiguous())
         # bf16 activations: weight grads come back fp32-accumulated
         return (gx, gW1.to(W1.dtype), gb1.to(b1.dtype), gW2.to(W2.dtype),
@@ -42,12 +50,20 @@ class _LiftHeadFn(torch.autograd.Function):
 
 
 def lift_head(x, W1, b1, W2, b2):
-    """x: [B, C, *sp, 1] -> [B, width, *sp, T_out], fully fused."""
+    """x: [B, C, *sp, T_in] -> [B, width, *sp, T_out], fully fused."""
     B, C = x.shape[0], x.shape[1]
     sp = x.shape[2:-1]
+    t_in = x.shape[-1]
     S = 1
     for d in sp:
         S *= d
-    x3 = x.reshape(B, C, S).contiguous()
-    out = _LiftHeadFn.apply(x3, W1, b1.reshape(-1), W2, b2.reshape(-1))
+    if t_in == 1 and W1.shape[0] <= 32:
+        # the T_in == 1 kernels take x with the unit time axis folded away
+        xs = x.reshape(B, C, S).contiguous()
+    else:
+        xs = x.reshape(B, C, S, t_in).contiguous()
+        # the general kernels read the weights in x's dtype (no-op casts
+        # for a model built in one dtype)
+        W1, b1, W2, b2 = (t.to(x.dtype) for t in (W1, b1, W2, b2))
+    out = _LiftHeadFn.apply(xs, W1, b1.reshape(-1), W2, b2.reshape(-1))
     return out.reshape(B, W2.shape[0], *sp, W1.shape[0])
