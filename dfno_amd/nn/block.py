@@ -21,19 +21,21 @@ MI355X-native differences:
 
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-import os
-
 from ..comm import (Repartition, _get_plan, repartition_complete,
                     repartition_issue)
 from ..partition import Partition, compute_distribution_info
-from ..ops import spectral_conv, add_gelu, linear_res_gelu, rfft_trunc, fft_trunc, pad_ifft, pad_irfft
-from ..ops import irfft_linear_res_gelu, fused_epilogue_enabled, fused_epilogue_ok
+from ..ops import spectral_conv, linear_res_gelu, rfft_trunc, fft_trunc, pad_ifft, pad_irfft
+from ..ops import block_epilogue, fused_epilogue_enabled, fused_epilogue_ok
+from ..ops.fft import (new_stash_key, rfft_bf16_native_ok, rfft_trunc_stash,
+                       stash_fusable, zt_caps_ok, zt_enabled, zt_fwd, zt_inv,
+                       zt_native_ok)
 from ..timing import comm_region
 from .linear import BroadcastedLinear
 
@@ -202,8 +204,43 @@ class DistributedFNOBlock(nn.Module):
         return torch.cat(pieces, dim=dim)
 
     # ---- per-phase transform helpers (shared by both forward paths) ------
-    def _fwd_m(self, x: torch.Tensor, saved: Dict[int, int]) -> torch.Tensor:
-        """rfft + truncation along the trailing (P_m-local) dims."""
+    def _zt_modes(self):
+        """``(z_dim, mz_lo, mz_hi, mt)`` of the fused (z,t) plane transform
+        (two trailing dims only)."""
+        z_dim, t_dim = self.dim_m
+        return (z_dim, self.restrict_prefixes[z_dim],
+                self.restrict_suffixes.get(z_dim, 0),
+                self.restrict_prefixes[t_dim])
+
+    def _zt_fwd_ok(self, x: torch.Tensor, stash: bool) -> bool:
+        """Whether the fused (z,t) analysis takes ``x``.  Its adjoint
+        accumulates a stashed gradient in fp32 only."""
+        if len(self.dim_m) != 2 or not zt_enabled():
+            return False
+        _, mzl, mzh, mt = self._zt_modes()
+        return (zt_native_ok(x, mzl, mzh, mt)
+                and (not stash or x.dtype == torch.float32))
+
+    def _stashes(self, x: torch.Tensor, r1_identity: bool) -> bool:
+        """Whether this forward folds the epilogue's gradient for the block
+        input into the adjoint of the chain's first transform (ops/fft.py
+        stash).  R1 must have been an identity, so that the block input
+        itself feeds that transform and its adjoint is the last producer of
+        the input gradient; a gradient must be wanted; and the transform
+        must have a stash-accumulating adjoint for this tensor."""
+        if not (r1_identity and x.is_cuda and x.numel() > 0
+                and torch.is_grad_enabled() and x.requires_grad):
+            return False
+        outermost = self.dim_m[-1]
+        return (self._zt_fwd_ok(x, stash=True)
+                or stash_fusable(x, outermost, self.restrict_prefixes[outermost]))
+
+    def _fwd_m(self, x: torch.Tensor, saved: Dict[int, int], stash_key=None):
+        """rfft + truncation along the trailing (P_m-local) dims: the fused
+        (z,t) plane kernel where it applies, the 1-D chain otherwise.  With a
+        ``stash_key`` (see ``_stashes``) the first transform's adjoint adds
+        the gradient stashed under it, and ``(spectrum, ordering token)`` is
+        returned instead of the spectrum."""
         if x.numel() == 0:
             # requires_grad in grad mode so the downstream comm ops keep a
             # rank-uniform backward graph (their adjoints must run on EVERY
@@ -211,31 +248,28 @@ class DistributedFNOBlock(nn.Module):
             return torch.empty(0, dtype=self.dtype_complex, device=x.device,
                                requires_grad=torch.is_grad_enabled())
         outermost = self.dim_m[-1]
-        if len(self.dim_m) == 2:
-            # fused (z,t) plane transform: both trailing dims in one kernel
-            from ..ops.fft import zt_enabled, zt_fwd, zt_native_ok
-            z_dim = self.dim_m[0]
-            mzl = self.restrict_prefixes[z_dim]
-            mzh = self.restrict_suffixes.get(z_dim, 0)
-            mt = self.restrict_prefixes[outermost]
-            if zt_enabled() and zt_native_ok(x, mzl, mzh, mt):
-                saved[outermost] = x.shape[outermost] // 2 + 1
-                saved[z_dim] = x.shape[z_dim]
-                return zt_fwd(x, mzl, mzh, mt)
-        if x.dtype == torch.bfloat16:
-            from ..ops.fft import rfft_bf16_native_ok
-            if not rfft_bf16_native_ok(x, outermost,
-                                       self.restrict_prefixes[outermost]):
+        mt = self.restrict_prefixes[outermost]
+        saved[outermost] = x.shape[outermost] // 2 + 1
+        if self._zt_fwd_ok(x, stash=stash_key is not None):
+            # both trailing dims in one kernel
+            z_dim, mzl, mzh, _ = self._zt_modes()
+            saved[z_dim] = x.shape[z_dim]
+            return zt_fwd(x, mzl, mzh, mt, stash_key=stash_key)
+        tok = None
+        if stash_key is not None:
+            x, tok = rfft_trunc_stash(x, outermost, mt, stash_key)
+        else:
+            if (x.dtype == torch.bfloat16
+                    and not rfft_bf16_native_ok(x, outermost, mt)):
                 # no bf16-IO kernel for this shape: boundary-cast to fp32
                 # (the spectral path runs fp32/c64 either way)
                 x = x.float()
-        saved[outermost] = x.shape[outermost] // 2 + 1
-        x = rfft_trunc(x, outermost, self.restrict_prefixes[outermost])
+            x = rfft_trunc(x, outermost, mt)
         for dim in reversed(self.dim_m[:-1]):
             saved[dim] = x.shape[dim]
             x = fft_trunc(x, dim, self.restrict_prefixes[dim],
                           self.restrict_suffixes.get(dim, 0))
-        return x
+        return x if stash_key is None else (x, tok)
 
     def _fwd_y(self, x: torch.Tensor, saved: Dict[int, int]) -> torch.Tensor:
         """fft + truncation along the leading (P_y-local) dims."""
@@ -265,29 +299,22 @@ class DistributedFNOBlock(nn.Module):
             return torch.empty(0, dtype=self.dtype, device=y.device,
                                requires_grad=torch.is_grad_enabled())
         outermost = self.dim_m[-1]
-        if defer_irfft:
-            for dim in self.dim_m[:-1]:
-                y = pad_ifft(y, dim, saved[dim],
-                             self.restrict_prefixes[dim],
-                             self.restrict_suffixes.get(dim, 0))
-            return y
-        if len(self.dim_m) == 2 and y.is_cuda and y.dtype == torch.complex64:
-            from ..ops.fft import zt_enabled, zt_inv
-            z_dim = self.dim_m[0]
-            mzl = self.restrict_prefixes[z_dim]
-            mzh = self.restrict_suffixes.get(z_dim, 0)
-            Z, T = saved[z_dim], self.in_shape[-1]
-            if (zt_enabled() and Z <= 64 and T <= 64
-                    and mzl + mzh <= min(48, Z)
-                    and y.shape[-1] <= 32 and y.shape[-2] == mzl + mzh):
+        T = self.in_shape[-1]
+        if (not defer_irfft and len(self.dim_m) == 2 and zt_enabled()
+                and y.is_cuda and y.dtype == torch.complex64):
+            z_dim, mzl, mzh, mt = self._zt_modes()
+            Z = saved[z_dim]
+            if (zt_caps_ok(self.dtype, Z, T, mzl, mzh, mt)
+                    and y.shape[-2] == mzl + mzh):
                 return zt_inv(y, Z, T, mzl, mzh, out_dtype=self.dtype)
         for dim in self.dim_m[:-1]:
             y = pad_ifft(y, dim, saved[dim],
                          self.restrict_prefixes[dim],
                          self.restrict_suffixes.get(dim, 0))
-        y = pad_irfft(y, outermost, saved[outermost],
-                      self.in_shape[-1], self.restrict_prefixes[outermost],
-                      out_dtype=self.dtype)
+        if defer_irfft:
+            return y
+        y = pad_irfft(y, outermost, saved[outermost], T,
+                      self.restrict_prefixes[outermost], out_dtype=self.dtype)
         # (bf16 models: the c2r kernel emits bf16 directly; the exchange in
         # R4 then moves bf16.  Anything else lands here as a no-op.)
         return y.to(self.dtype) if y.dtype != self.dtype else y
@@ -322,9 +349,10 @@ class DistributedFNOBlock(nn.Module):
         (ops/epilogue.py) instead of materializing the real activation.
 
         Needs R4 to be an identity (the spectrum is already laid out like
-        the block output) and the fp32 kernel range; like the chunk policy
-        it reads GLOBAL configuration only, so every rank agrees.
-        DFNO_FUSED_EPILOGUE=0 restores the two-kernel path.
+        the block output), the fp32 kernel range, and the fused (z,t)
+        synthesis not to own the inverse (DFNO_ZT=1 within its caps); like
+        the chunk policy it reads GLOBAL configuration only, so every rank
+        agrees.  DFNO_FUSED_EPILOGUE=0 restores the two-kernel path.
         """
         if not fused_epilogue_enabled():
             return False
@@ -332,10 +360,12 @@ class DistributedFNOBlock(nn.Module):
         m = min(self.restrict_prefixes[self.dim_m[-1]], T // 2 + 1)
         if not fused_epilogue_ok(self.dtype, self.width, self.width, T, m):
             return False
-        if len(self.dim_m) == 2:
-            from ..ops.fft import zt_enabled
-            if zt_enabled():        # fused (z,t) synthesis owns the irfft
-                return False
+        if len(self.dim_m) == 2 and zt_enabled():
+            # the trailing dims are whole on P_m, so their global extents
+            # are the ones the (z,t) kernels would see
+            z_dim, mzl, mzh, mt = self._zt_modes()
+            if zt_caps_ok(self.dtype, self.in_shape[z_dim], T, mzl, mzh, mt):
+                return False    # fused (z,t) synthesis owns the irfft
         return _get_plan(self.P_m, self.P_x, tuple(self.in_shape)).is_identity
 
     def _chunk_sizes(self, nch: int):
@@ -361,83 +391,35 @@ class DistributedFNOBlock(nn.Module):
         # up front, dfno.py:244) is deferred and fused into the epilogue as
         # gelu(W x_in + y) — no y0 tensor is materialized.  Its weight is
         # broadcast here so the collective order matches the reference.
-        x_in = x
         with comm_region() as r:
             W_res = self.linear.W_bcast(self.linear.W)  # residual weight only
         self.linear.dt_comm = r.host_dt                 # (bias=False)
 
         nch = self._pipeline_chunks()
         if nch > 1:
-            y = self._forward_pipelined(x, nch)
-        else:
-            y, x_in, spectrum, stash = self._forward_seq(x)
-            if spectrum:
-                # y is the kept-mode time spectrum: irfft fused into the
-                # epilogue, the real chain output never reaches HBM.  With
-                # a stash entry the epilogue routes its grad-x into the
-                # rfft adjoint itself (as (gz, W) for the fused adjoint
-                # kernel where it applies, through the alias otherwise).
-                T = self.in_shape[-1]
-                return irfft_linear_res_gelu(
-                    x_in, W_res, y, T // 2 + 1, T,
-                    self.restrict_prefixes[self.dim_m[-1]], stash=stash)
+            return linear_res_gelu(x, W_res, self._forward_pipelined(x, nch))
+        return self._forward_seq(x, W_res)
 
-        return linear_res_gelu(x_in, W_res, y)
+    def _forward_seq(self, x: torch.Tensor, W_res: torch.Tensor) -> torch.Tensor:
+        """The pencil chain and its epilogue, one exchange at a time.
 
-    def _forward_seq(self, x: torch.Tensor):
-        """Returns (chain output, epilogue input, spectrum flag, stash).
-        The epilogue input is either ``x`` itself or its StashGradFn alias
-        when the residual input-gradient fuses into the rfft adjoint
-        (ops/fft.py stash).  With the flag set the chain output is still
-        the kept-mode time spectrum (see ``_fuse_epilogue``); ``stash`` is
-        then the rfft's ``(key, token)`` where one is open and the alias
-        has NOT been made — the fused epilogue owns that choice."""
-        from ..ops.fft import (StashGradFn, new_stash_key, rfft_trunc_stash,
-                               stash_fusable)
-
+        Where the block input itself feeds the first transform
+        (``_stashes``), that transform hands out a ``(key, token)`` stash and
+        the epilogue (``ops.block_epilogue``) routes its gradient for the
+        input into the transform's adjoint.  Where ``_fuse_epilogue`` holds,
+        the chain stops at the kept-mode time spectrum and the epilogue
+        synthesizes the irfft itself; R4 is an identity there."""
         saved: Dict[int, int] = {}   # pre-truncation extent per dim
-        x_orig = x
+        x_in = x
         with comm_region() as r:
             x = self.R1(x)
         self.dt_comm += r.host_dt
 
-        x_epi = x_orig
         stash = None
-        outermost = self.dim_m[-1]
-        zt_stash = False
-        if (x is x_orig and len(self.dim_m) == 2 and x.is_cuda
-                and x.numel() > 0 and x.dtype == torch.float32
-                and torch.is_grad_enabled() and x.requires_grad):
-            from ..ops.fft import zt_enabled, zt_fwd, zt_native_ok
-            z_dim = self.dim_m[0]
-            mzl = self.restrict_prefixes[z_dim]
-            mzh = self.restrict_suffixes.get(z_dim, 0)
-            mt = self.restrict_prefixes[outermost]
-            if zt_enabled() and zt_native_ok(x, mzl, mzh, mt):
-                # fused (z,t) transform + residual-grad stash in its adjoint
-                key = new_stash_key()
-                saved[outermost] = x.shape[outermost] // 2 + 1
-                saved[z_dim] = x.shape[z_dim]
-                xm, tok = zt_fwd(x, mzl, mzh, mt, stash_key=key)
-                x_epi = StashGradFn.apply(x_orig, tok, key)
-                x = xm
-                zt_stash = True
-        if zt_stash:
-            pass
-        elif (x is x_orig
-                and stash_fusable(x, outermost, self.restrict_prefixes[outermost])):
-            # R1 is an identity here: the chain's input-grad producer is the
-            # rfft adjoint — fold the epilogue's gradient into its writeback
+        if self._stashes(x, r1_identity=x is x_in):
             key = new_stash_key()
-            saved[outermost] = x.shape[outermost] // 2 + 1
-            xm, tok = rfft_trunc_stash(x, outermost,
-                                       self.restrict_prefixes[outermost], key)
-            for dim in reversed(self.dim_m[:-1]):
-                saved[dim] = xm.shape[dim]
-                xm = fft_trunc(xm, dim, self.restrict_prefixes[dim],
-                               self.restrict_suffixes.get(dim, 0))
-            stash = (key, tok)      # alias made below, or by the epilogue
-            x = xm
+            x, tok = self._fwd_m(x, saved, stash_key=key)
+            stash = (key, tok)
         else:
             x = self._fwd_m(x, saved)
 
@@ -461,14 +443,16 @@ class DistributedFNOBlock(nn.Module):
                  and self._fuse_epilogue())
         y = self._inv_m(y, saved, defer_irfft=defer)
         if defer:
-            return y, x_epi, True, stash    # R4 is an identity on this path
-        if stash is not None:
-            x_epi = StashGradFn.apply(x_orig, stash[1], stash[0])
+            # the real chain output never reaches HBM
+            T = self.in_shape[-1]
+            return block_epilogue(
+                x_in, W_res, y, stash=stash,
+                irfft=(T // 2 + 1, T, self.restrict_prefixes[self.dim_m[-1]]))
 
         with comm_region() as r:
             y = self.R4(y)
         self.dt_comm += r.host_dt
-        return y, x_epi, False, None
+        return block_epilogue(x_in, W_res, y, stash=stash)
 
     def _forward_pipelined(self, x: torch.Tensor, nch: int) -> torch.Tensor:
         """Channel-chunked software pipeline over the pencil chain.

@@ -3,5 +3,5 @@ from .spectral import spectral_conv
 from .projhead import proj_head, proj_head_supported
 from .fft import rfft_trunc, fft_trunc, pad_ifft, pad_irfft
 from .lifthead import lift_head, lift_head_supported
-from .epilogue import (irfft_linear_res_gelu, fused_epilogue_enabled,
-                       fused_epilogue_ok)
+from .epilogue import (block_epilogue, irfft_linear_res_gelu,
+                       fused_epilogue_enabled, fused_epilogue_ok)

@@ -1,6 +1,10 @@
-"""Block epilogue with the time-axis irfft fused in.
+"""Block epilogue, with the time-axis irfft fused in where it applies.
 
-``irfft_linear_res_gelu(x, W, Yt, n_half, n_out, m)`` computes
+``block_epilogue(x, W, y, stash=, irfft=)`` is the single entry for the FNO
+block's ``gelu(W @_channel x + y)``, and the single place that decides how a
+stashed input gradient is routed: it alone creates the ``StashGradFn`` alias.
+Given ``irfft`` (``irfft_linear_res_gelu(x, W, Yt, n_half, n_out, m)`` is
+that spelling) it computes
 
     gelu(W @_channel x + pad_irfft(Yt, -1, n_half, n_out, m))
 
@@ -11,8 +15,9 @@ per line where the real line is n_out) and synthesizes each output on the
 fly.  ``need_z`` follows autograd: a no-grad forward skips the
 pre-activation store as well.
 
-Backward reuses the existing native kernels: the fused trunk mix backward
-(or its three-kernel composition off the 20x20 shape) for ``gx, gW, gz`` and
+Backward reuses the existing native kernels through the shared
+``pointwise.mix_backward`` (the fused trunk mix backward, or its three-kernel
+composition off the 20x20 shape) for ``gx, gW, gz``, and
 ``dft_pad_irfft_adj(gz)`` for the spectrum gradient.
 
 With a stash entry (the block's arrangement: ``x`` also feeds the chain's
@@ -35,9 +40,9 @@ import torch
 
 from .. import _ext
 from .fft import _GRAD_STASH, StashGradFn, pad_irfft
-from .pointwise import linear_res_gelu
+from .pointwise import linear_res_gelu, mix_backward
 
-__all__ = ["irfft_linear_res_gelu", "fused_epilogue_enabled",
+__all__ = ["block_epilogue", "irfft_linear_res_gelu", "fused_epilogue_enabled",
            "fused_epilogue_ok", "fused_rfft_adj_enabled", "rfft_adj_mix_ok"]
 
 
@@ -103,71 +108,72 @@ class _IrfftLinearResGeluFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        ext = _ext.get(required=True)
         x3, W, z3 = ctx.saved_tensors
-        gy = gy.contiguous()
         B, I, S = x3.shape
-        O = W.shape[0]
-        m = ctx.y_shape[-1]
-        if ctx.key is not None:
-            # grad-x deferred to the rfft adjoint (rfft_adj_mix): gz, gW only
-            if I == 20 and O == 20:
-                _, gW, _, gz = ext.channel_mix_bwd_fused(gy, z3, x3, W,
-                                                         False, True, False)
-            else:
-                gz = ext.gelu_bwd(gy, z3)
-                gW, _ = ext.channel_mix_bwd_w(gz, x3, False)
+        deferred = ctx.key is not None
+        gx, gW, _, gz = mix_backward(gy.contiguous(), z3, x3, W, act=True,
+                                     want_gz=True, want_gx=not deferred)
+        gtok = None
+        if deferred:
+            # grad-x is left to the rfft adjoint (rfft_adj_mix)
             _GRAD_STASH[ctx.key] = (gz, W)
-            gY = ext.dft_pad_irfft_adj(
-                gz.reshape(B, O, S // ctx.n_out, ctx.n_out), 3, m)
-            return (None, gW.to(W.dtype), gY.reshape(ctx.y_shape), None,
-                    None, torch.empty(0, device=gy.device))
-        if I == 20 and O == 20:
-            # trunk 20x20: one kernel; gz comes back as the residual grad
-            gx, gW, _, gz = ext.channel_mix_bwd_fused(gy, z3, x3, W,
-                                                      False, True)
+            gtok = torch.empty(0, device=gy.device)
         else:
-            gz = ext.gelu_bwd(gy, z3)
-            gx = ext.channel_mix_fwd_t(gz, W)
-            gW, _ = ext.channel_mix_bwd_w(gz, x3, False)
-        gY = ext.dft_pad_irfft_adj(gz.reshape(B, O, S // ctx.n_out, ctx.n_out),
-                                   3, m)
-        return (gx.reshape(ctx.x_shape), gW.to(W.dtype),
-                gY.reshape(ctx.y_shape), None, None, None)
+            gx = gx.reshape(ctx.x_shape)
+        gY = _ext.get(required=True).dft_pad_irfft_adj(
+            gz.reshape(B, W.shape[0], S // ctx.n_out, ctx.n_out), 3,
+            ctx.y_shape[-1])
+        return gx, gW, gY.reshape(ctx.y_shape), None, None, gtok
+
+
+def block_epilogue(x: torch.Tensor, W: torch.Tensor, y: torch.Tensor,
+                   stash=None, irfft=None) -> torch.Tensor:
+    """The FNO block's epilogue ``gelu(W @_channel x + y)``.
+
+    ``irfft = (n_half, n_out, m)``: ``y`` is still the kept-mode time
+    spectrum ``[..., min(m, n_half)]`` as ``pad_irfft`` takes it, and the
+    synthesis runs inside the fused kernel where it covers the shape.
+
+    ``stash = (key, tok)`` from the transform that consumed ``x`` at the head
+    of the chain (``rfft_trunc_stash`` / ``zt_fwd(stash_key=)``): the gradient
+    for ``x`` is not returned to the engine but folded into that transform's
+    adjoint.  This is the one place that chooses how — as ``(gz, W)`` for
+    ``rfft_adj_mix`` where the fused kernel and its adjoint mode cover the
+    shape (detached ``x``, no alias), through a ``StashGradFn`` alias (the
+    stashed ``gx``) otherwise.  A ``zt_fwd`` stash takes a tensor only, so
+    it never comes with ``irfft`` (the (z,t) synthesis owns the inverse
+    wherever the (z,t) analysis ran)."""
+    fused = False
+    if irfft is not None:
+        n_half, n_out, m = irfft
+        m = min(m, n_half)
+        fused = (x.is_cuda and x.numel() > 0 and y.dtype == torch.complex64
+                 and y.shape[-1] == m and x.shape[-1] == n_out
+                 and fused_epilogue_ok(x.dtype, x.shape[1], W.shape[0],
+                                       n_out, m))
+    key = tok = None
+    if stash is not None:
+        if (fused and fused_rfft_adj_enabled()
+                and rfft_adj_mix_ok(x.dtype, x.shape[1], W.shape[0], n_out, m)):
+            x = x.detach()
+            key, tok = stash
+        else:
+            x = StashGradFn.apply(x, stash[1], stash[0])
+    if fused:
+        out = _IrfftLinearResGeluFn.apply(x, W, y, n_out, key, tok)
+        shape = list(x.shape)
+        shape[1] = W.shape[0]
+        return out.reshape(shape)
+    if irfft is not None:
+        y = pad_irfft(y, -1, n_half, n_out, m, out_dtype=x.dtype)
+        if y.dtype != x.dtype:
+            y = y.to(x.dtype)
+    return linear_res_gelu(x, W, y)
 
 
 def irfft_linear_res_gelu(x: torch.Tensor, W: torch.Tensor, Yt: torch.Tensor,
                           n_half: int, n_out: int, m: int,
                           stash=None) -> torch.Tensor:
-    """gelu(W @_channel x + pad_irfft(Yt)) over the trailing (time) dim.
-
-    ``Yt`` holds the kept low modes ``[..., min(m, n_half)]`` of the
-    half-spectrum, as ``pad_irfft`` takes them.
-
-    ``stash = (key, tok)`` from ``rfft_trunc_stash(x, -1, m, key)``: the
-    gradient for ``x`` is not returned but folded into that rfft's adjoint —
-    as ``(gz, W)`` for ``rfft_adj_mix`` where the kernel covers the shape,
-    through a ``StashGradFn`` alias (today's stashed ``gx``) otherwise."""
-    m = min(m, n_half)
-    fused = (x.is_cuda and x.numel() > 0 and Yt.dtype == torch.complex64
-             and Yt.shape[-1] == m and x.shape[-1] == n_out
-             and fused_epilogue_ok(x.dtype, x.shape[1], W.shape[0], n_out, m))
-    if stash is not None:
-        key, tok = stash
-        if (fused and fused_rfft_adj_enabled()
-                and rfft_adj_mix_ok(x.dtype, x.shape[1], W.shape[0], n_out, m)):
-            out = _IrfftLinearResGeluFn.apply(x.detach(), W, Yt, n_out,
-                                              key, tok)
-            shape = list(x.shape)
-            shape[1] = W.shape[0]
-            return out.reshape(shape)
-        x = StashGradFn.apply(x, tok, key)
-    if fused:
-        out = _IrfftLinearResGeluFn.apply(x, W, Yt, n_out)
-        shape = list(x.shape)
-        shape[1] = W.shape[0]
-        return out.reshape(shape)
-    res = pad_irfft(Yt, -1, n_half, n_out, m, out_dtype=x.dtype)
-    if res.dtype != x.dtype:
-        res = res.to(x.dtype)
-    return linear_res_gelu(x, W, res)
+    """gelu(W @_channel x + pad_irfft(Yt)) over the trailing (time) dim:
+    ``block_epilogue`` on a spectrum, ``stash`` as described there."""
+    return block_epilogue(x, W, Yt, stash=stash, irfft=(n_half, n_out, m))

@@ -18,6 +18,13 @@ truncation, and their autograd mirrors (~25 ms/step at the flagship config).
 
 Fallback (CPU, N > 64, or unsupported dtype) composes differentiable
 torch.fft ops with identical semantics.
+
+Two more things live here.  The residual-gradient stash: ``rfft_trunc_stash``
+and ``zt_fwd(stash_key=)`` return an ordering token next to the spectrum, and
+their adjoints add what the block epilogue left under the key; the second
+consumer is wired up by ``ops.epilogue.block_epilogue`` alone, which is the
+only caller of ``StashGradFn``.  And the fused (z,t) plane transforms of
+csrc/dft2d.hip, whose caps are stated once, in ``zt_caps_ok``.
 """
 
 from __future__ import annotations
@@ -251,7 +258,7 @@ class _RfftTruncStashFn(torch.autograd.Function):
 def rfft_trunc_stash(x, dim, m, key):
     """Native rfft_trunc variant returning (y, ordering-token) whose adjoint
     adds the gradient stashed under ``key``.  Caller must route the block
-    input's second use through ``StashGradFn(x, tok, key)``."""
+    input's second use through ``block_epilogue(..., stash=(key, tok))``."""
     d = dim % x.dim()
     m = min(m, x.shape[d] // 2 + 1)
     return _RfftTruncStashFn.apply(x, d, m, key)
@@ -306,14 +313,20 @@ def zt_enabled() -> bool:
     return os.environ.get("DFNO_ZT", "0") == "1"
 
 
-def zt_native_ok(x, mz_lo, mz_hi, mt) -> bool:
-    if not x.is_cuda or x.dim() < 2:
-        return False
-    Z, T = x.shape[-2], x.shape[-1]
-    mt = min(mt, T // 2 + 1)
-    return (x.dtype in (torch.float32, torch.bfloat16)
+def zt_caps_ok(dtype, Z, T, mz_lo, mz_hi, mt) -> bool:
+    """The caps of csrc/dft2d.hip, stated once: real IO dtype (the spectrum
+    side is complex64), plane extents and kept-mode counts.  Both kernels
+    and every policy that must know whether they own the (z,t) transforms
+    test this, next to ``zt_enabled()``."""
+    return (dtype in (torch.float32, torch.bfloat16)
             and Z <= 64 and T <= 64 and mz_lo + mz_hi <= min(48, Z)
-            and mt <= 32)
+            and min(mt, T // 2 + 1) <= 32)
+
+
+def zt_native_ok(x, mz_lo, mz_hi, mt) -> bool:
+    return (x.is_cuda and x.dim() >= 2
+            and zt_caps_ok(x.dtype, x.shape[-2], x.shape[-1],
+                           mz_lo, mz_hi, mt))
 
 
 class _ZtFwdFn(torch.autograd.Function):

@@ -72,6 +72,75 @@ def _gelu_grad(z: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# channel-mix backward: y = act(W x + ...) with pre-activation z.  Each step
+# owns its dispatch (fp32/fp64 native kernel, bf16 kernel within its caps,
+# torch composition); mix_backward is the one entry the autograd Functions
+# here and in ops/epilogue.py share.
+# ---------------------------------------------------------------------------
+
+def _gelu_bwd(gy: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """gz = gy * gelu'(z)."""
+    if gy.is_cuda and _native_dt(gy):
+        return _ext.get(required=True).gelu_bwd(gy, z)
+    if gy.is_cuda and gy.dtype == torch.bfloat16 and gy.numel() % 8 == 0:
+        return _ext.get(required=True).bf16_gelu_bwd(gy, z.contiguous())
+    return gy * _gelu_grad(z)
+
+
+def _mix_bwd_x(gz: torch.Tensor, W: torch.Tensor, op: str) -> torch.Tensor:
+    """gx[b,i,s] = sum_o W[o,i] gz[b,o,s]."""
+    if gz.is_cuda and _native_dt(gz):
+        return _ext.get(required=True).channel_mix_fwd_t(gz, W)
+    if _bf16_mix_ok(gz, W.shape[0], W.shape[1], op):
+        gx, _ = _ext.get(required=True).bf16_channel_mix(
+            gz.contiguous(), W.contiguous(), _ebf(gz.device), False, True,
+            False, _ebf(gz.device))
+        return gx
+    return torch.einsum("oi,bos->bis", W, gz)
+
+
+def _mix_bwd_w(gz: torch.Tensor, x3: torch.Tensor, W: torch.Tensor,
+               want_bias: bool):
+    """gW[o,i] = sum_bs gz[b,o,s] x[b,i,s], gb[o] = sum_bs gz[b,o,s]."""
+    I, O, S = x3.shape[1], W.shape[0], x3.shape[2]
+    if gz.is_cuda and _native_dt(gz) and I <= 32:
+        gW, gb = _ext.get(required=True).channel_mix_bwd_w(
+            gz.contiguous(), x3.contiguous(), want_bias)
+    elif (gz.is_cuda and gz.dtype == torch.bfloat16 and I <= 32 and O <= 128
+          and S % 128 == 0):
+        gW, gb = _ext.get(required=True).bf16_channel_mix_bwd_w(
+            gz.contiguous(), x3.contiguous(), want_bias)
+        gW, gb = gW.to(W.dtype), gb.to(W.dtype)
+    else:
+        gW = torch.einsum("bos,bis->oi", gz, x3)
+        gb = gz.sum(dim=(0, 2)) if want_bias else None
+    return gW, gb if want_bias else None
+
+
+def mix_backward(gy, z3, x3, W, *, act: bool, want_bias: bool = False,
+                 want_gz: bool = False, want_gx: bool = True,
+                 op: str = "channel_mix_bwd"):
+    """Backward of ``y = act(W x + ...)`` with ``gy, z3, x3`` as ``[B,*,S]``
+    and contiguous ``gy``: returns ``(gx, gW, gb, gz)``, with ``None`` for
+    whatever was not asked for.  ``op`` names the caller in fallback notes."""
+    if (act and gy.is_cuda and gy.dtype in (torch.float32, torch.bfloat16)
+            and x3.shape[1] == 20 and W.shape[0] == 20
+            and gy.dtype == x3.dtype):
+        # trunk 20x20: one kernel (mix_bwd.hip); gz exists only if wanted,
+        # and without want_gx the grad-x MFMA phase and store are skipped
+        gx, gW, gb, gz = _ext.get(required=True).channel_mix_bwd_fused(
+            gy, z3.contiguous(), x3.contiguous(), W.contiguous().float(),
+            want_bias, want_gz, *(() if want_gx else (False,)))
+        return (gx if want_gx else None, gW.to(W.dtype),
+                gb.to(W.dtype) if want_bias else None,
+                gz if want_gz else None)
+    gz = _gelu_bwd(gy, z3) if act else gy
+    gx = _mix_bwd_x(gz, W, op) if want_gx else None
+    gW, gb = _mix_bwd_w(gz, x3, W, want_bias)
+    return gx, gW, gb, gz if want_gz else None
+
+
+# ---------------------------------------------------------------------------
 # channel-contraction (dim=1) fused linear+bias+gelu
 # ---------------------------------------------------------------------------
 
@@ -106,59 +175,8 @@ class _ChannelMixFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x3, W, z3 = ctx.saved_tensors
-        act = ctx.act
-        gy = gy.contiguous()
-        if (act and gy.is_cuda and gy.dtype in (torch.float32, torch.bfloat16)
-                and x3.shape[1] == 20 and W.shape[0] == 20
-                and gy.dtype == x3.dtype):
-            # trunk 20x20: one kernel, gz never materialized (mix_bwd.hip)
-            ext = _ext.get(required=True)
-            gx, gW, gb, _ = ext.channel_mix_bwd_fused(
-                gy, z3.contiguous(), x3.contiguous(),
-                W.contiguous().float(), ctx.has_bias, False)
-            return (gx.reshape(ctx.x_shape), gW.to(W.dtype),
-                    gb.to(W.dtype) if ctx.has_bias else None, None)
-        is_bf16 = gy.is_cuda and gy.dtype == torch.bfloat16
-        bf16_ok = is_bf16 and _bf16_mix_ok(gy.reshape(x3.shape[0], W.shape[0], -1),
-                                           W.shape[0], x3.shape[1], "channel_mix_bwd")
-        if act:
-            if gy.is_cuda and _native_dt(gy):
-                ext = _ext.get(required=True)
-                gz = ext.gelu_bwd(gy, z3)
-            elif is_bf16 and gy.numel() % 8 == 0:
-                ext = _ext.get(required=True)
-                gz = ext.bf16_gelu_bwd(gy, z3.contiguous())
-            else:
-                gz = gy * _gelu_grad(z3)
-        else:
-            gz = gy
-        # grad x: contraction with W^T
-        if gy.is_cuda and _native_dt(gy):
-            ext = _ext.get(required=True)
-            gx = ext.channel_mix_fwd_t(gz, W)  # sum_o W[o,i] gz[b,o,s]
-        elif bf16_ok:
-            ext = _ext.get(required=True)
-            gx, _ = ext.bf16_channel_mix(gz.contiguous(), W.contiguous(),
-                                         _ebf(gy.device), False, True, False,
-                                         _ebf(gy.device))
-        else:
-            gx = torch.einsum("oi,bos->bis", W, gz)
-        # grad W / b
-        if gy.is_cuda and _native_dt(gy) and x3.shape[1] <= 32:
-            ext = _ext.get(required=True)
-            gW, gb = ext.channel_mix_bwd_w(gz.contiguous(), x3, ctx.has_bias)
-            if not ctx.has_bias:
-                gb = None
-        elif (is_bf16 and x3.shape[1] <= 32 and W.shape[0] <= 128
-              and x3.shape[2] % 128 == 0):
-            ext = _ext.get(required=True)
-            gW, gb = ext.bf16_channel_mix_bwd_w(gz.contiguous(), x3.contiguous(),
-                                                ctx.has_bias)
-            gW = gW.to(W.dtype)
-            gb = gb.to(W.dtype) if ctx.has_bias else None
-        else:
-            gW = torch.einsum("bos,bis->oi", gz, x3)
-            gb = gz.sum(dim=(0, 2)) if ctx.has_bias else None
+        gx, gW, gb, _ = mix_backward(gy.contiguous(), z3, x3, W, act=ctx.act,
+                                     want_bias=ctx.has_bias)
         return gx.reshape(ctx.x_shape), gW, gb, None
 
 
@@ -237,40 +255,9 @@ class _LinearResGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x3, W, z3 = ctx.saved_tensors
-        gy = gy.contiguous()
-        if (gy.is_cuda and gy.dtype in (torch.float32, torch.bfloat16)
-                and x3.shape[1] == 20 and W.shape[0] == 20
-                and gy.dtype == x3.dtype):
-            # trunk 20x20: one kernel; gz comes back as the residual grad
-            ext = _ext.get(required=True)
-            gx, gW, _, gz = ext.channel_mix_bwd_fused(
-                gy, z3.contiguous(), x3.contiguous(),
-                W.contiguous().float(), False, True)
-            return (gx.reshape(ctx.x_shape), gW.to(W.dtype),
-                    gz.reshape(ctx.res_shape))
-        if gy.is_cuda and _native_dt(gy):
-            ext = _ext.get(required=True)
-            gz = ext.gelu_bwd(gy, z3)
-            gx = ext.channel_mix_fwd_t(gz, W)
-            if x3.shape[1] <= 32:
-                gW, _ = ext.channel_mix_bwd_w(gz, x3.contiguous(), False)
-            else:
-                gW = torch.einsum("bos,bis->oi", gz, x3)
-        elif _bf16_mix_ok(x3, W.shape[0], x3.shape[1], "linear_res_gelu_bwd"):
-            ext = _ext.get(required=True)
-            gz = ext.bf16_gelu_bwd(gy, z3.contiguous())
-            gx, _ = ext.bf16_channel_mix(gz, W.contiguous(), _ebf(gy.device),
-                                         False, True, False, _ebf(gy.device))
-            if (x3.shape[1] <= 32 and W.shape[0] <= 128
-                    and x3.shape[2] % 128 == 0):
-                gW, _ = ext.bf16_channel_mix_bwd_w(gz, x3.contiguous(), False)
-                gW = gW.to(W.dtype)
-            else:
-                gW = torch.einsum("bos,bis->oi", gz, x3)
-        else:
-            gz = gy * _gelu_grad(z3)
-            gx = torch.einsum("oi,bos->bis", W, gz)
-            gW = torch.einsum("bos,bis->oi", gz, x3)
+        # gz is the residual grad as well
+        gx, gW, _, gz = mix_backward(gy.contiguous(), z3, x3, W, act=True,
+                                     want_gz=True, op="linear_res_gelu_bwd")
         return gx.reshape(ctx.x_shape), gW, gz.reshape(ctx.res_shape)
 
 
@@ -304,15 +291,7 @@ class _AddGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (z,) = ctx.saved_tensors
-        gy = gy.contiguous()
-        if gy.is_cuda and _native_dt(gy):
-            ext = _ext.get(required=True)
-            gz = ext.gelu_bwd(gy, z)
-        elif gy.is_cuda and gy.dtype == torch.bfloat16 and gy.numel() % 8 == 0:
-            ext = _ext.get(required=True)
-            gz = ext.bf16_gelu_bwd(gy, z.contiguous())
-        else:
-            gz = gy * _gelu_grad(z)
+        gz = _gelu_bwd(gy.contiguous(), z)
         return gz, gz
 
 
@@ -338,14 +317,7 @@ class _GeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        gy = gy.contiguous()
-        if gy.is_cuda and _native_dt(gy):
-            ext = _ext.get(required=True)
-            return ext.gelu_bwd(gy, x)
-        if gy.is_cuda and gy.dtype == torch.bfloat16 and gy.numel() % 8 == 0:
-            ext = _ext.get(required=True)
-            return ext.bf16_gelu_bwd(gy, x.contiguous())
-        return gy * _gelu_grad(x)
+        return _gelu_bwd(gy.contiguous(), x)
 
 
 def gelu(x: torch.Tensor) -> torch.Tensor:
