@@ -42,7 +42,9 @@ def _find_prebuilt():
     for suffix in (".so",):
         cand = _BUILD / f"{_EXT_NAME}{suffix}"
         if cand.exists():
-            srcs_mtime = max((s.stat().st_mtime for s in SOURCES if s.exists()), default=0.0)
+            # every file in csrc/: the headers are compiled into the .so too
+            srcs = set(SOURCES) | {f for f in _CSRC.glob("*") if f.is_file()}
+            srcs_mtime = max((s.stat().st_mtime for s in srcs if s.exists()), default=0.0)
             if cand.stat().st_mtime >= srcs_mtime:
                 return cand
     return None

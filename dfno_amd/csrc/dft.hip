@@ -27,8 +27,11 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include "kernels.h"
+#include "device_util.h"
 
 namespace {
+
+using namespace dfno_io;
 
 constexpr int kBlock = 256;
 constexpr int kMaxN = 64;    // cap of the fully-tuned N<=64 paths
@@ -56,18 +59,6 @@ __device__ __forceinline__ void cmul_acc(T& cr, T& ci, T sr, T si) {
   T nr = cr * sr - ci * si;
   T ni = cr * si + ci * sr;
   cr = nr; ci = ni;
-}
-
-// bf16 <-> f32 helpers for the bf16-IO transform variants (the bf16 model's
-// real-side activations enter/leave the spectral path in bf16 storage;
-// arithmetic stays fp32 — see csrc/bf16.hip for the rationale)
-__device__ __forceinline__ float dft_b2f(unsigned short h) {
-  return __uint_as_float(((unsigned int)h) << 16);
-}
-
-__device__ __forceinline__ unsigned int dft_f2b2(float lo, float hi) {
-  __hip_bfloat162 h2 = __float22bfloat162_rn(float2{lo, hi});
-  return *reinterpret_cast<unsigned int*>(&h2);
 }
 
 // kept-mode k value for index ki
@@ -709,7 +700,7 @@ __global__ __launch_bounds__(kBlock) void dft_r2c_glds_kernel(
       if (NT == 0 && j >= N) break;
       T x;
       if constexpr (std::is_same<TI, unsigned short>::value)
-        x = dft_b2f(src[j]);
+        x = b2f(src[j]);
       else
         x = (T)src[j];
       auto twj = (const __attribute__((address_space(4))) T*)
@@ -774,13 +765,13 @@ __global__ __launch_bounds__(LB) void dft_r2c_last_kernel(
           const unsigned int w[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            tile[idx + 2 * k] = (T)dft_b2f((unsigned short)(w[k] & 0xffffu));
-            tile[idx + 2 * k + 1] = (T)dft_b2f((unsigned short)(w[k] >> 16));
+            tile[idx + 2 * k] = (T)b2f((unsigned short)(w[k] & 0xffffu));
+            tile[idx + 2 * k + 1] = (T)b2f((unsigned short)(w[k] >> 16));
           }
         }
       } else {
         for (int idx = threadIdx.x; idx < nl * N; idx += LB)
-          tile[idx] = (T)dft_b2f(in[base + idx]);
+          tile[idx] = (T)b2f(in[base + idx]);
       }
     } else if constexpr (std::is_same<T, float>::value) {
       const long base = l0 * N;
@@ -925,21 +916,21 @@ __global__ __launch_bounds__(LB) void dft_c2r_last_kernel(
             const unsigned int w[4] = {a8.x, a8.y, a8.z, a8.w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              v[2 * q] += dft_b2f((unsigned short)(w[q] & 0xffffu));
-              v[2 * q + 1] += dft_b2f((unsigned short)(w[q] >> 16));
+              v[2 * q] += b2f((unsigned short)(w[q] & 0xffffu));
+              v[2 * q + 1] += b2f((unsigned short)(w[q] >> 16));
             }
           }
           uint4 raw;
-          raw.x = dft_f2b2(v[0], v[1]);
-          raw.y = dft_f2b2(v[2], v[3]);
-          raw.z = dft_f2b2(v[4], v[5]);
-          raw.w = dft_f2b2(v[6], v[7]);
+          raw.x = f2b2(v[0], v[1]);
+          raw.y = f2b2(v[2], v[3]);
+          raw.z = f2b2(v[4], v[5]);
+          raw.w = f2b2(v[6], v[7]);
           *reinterpret_cast<uint4*>(out + base + idx) = raw;
         }
       } else {
         for (int idx = threadIdx.x; idx < nl * N; idx += LB) {
           float v = (float)tile[idx];
-          if (ab != nullptr) v += dft_b2f(ab[base + idx]);
+          if (ab != nullptr) v += b2f(ab[base + idx]);
           __hip_bfloat16 h = __float2bfloat16(v);
           out[base + idx] = *reinterpret_cast<unsigned short*>(&h);
         }
@@ -973,13 +964,6 @@ __global__ __launch_bounds__(LB) void dft_c2r_last_kernel(
   }
 }
 
-int grid_for_d(long work) {
-  long g = (work + kBlock - 1) / kBlock;
-  long cap = 256L * 16;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 void split_dims(const at::Tensor& x, int dim, long& outer, long& inner) {
   outer = 1;
@@ -1041,7 +1025,7 @@ at::Tensor dft_c2c(const at::Tensor& x, int64_t dim, int64_t n,
   if (x.numel() == 0) return out;
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = grid_for_d(outer * inner);
+  int grid = launch_grid(outer * inner, kBlock, 256L * 16);
 
   bool paired = (m_hi == m_lo) && (inner % 2 == 0) && m_lo <= 16;
   static const bool no_radix = []() {
@@ -1065,7 +1049,8 @@ at::Tensor dft_c2c(const at::Tensor& x, int64_t dim, int64_t n,
     while (Gsel < 8 && (n % (Gsel * 2) == 0) && pwork * Gsel < gtarget)
       Gsel *= 2;
   }
-  int grid2 = paired ? grid_for_d(outer * (inner / 2) * Gsel) : grid;
+  int grid2 = paired ? launch_grid(outer * (inner / 2) * Gsel, kBlock, 256L * 16)
+                     : grid;
 #define DFT_LG(KERNEL, LC, ...)                                                \
   switch (Gsel) {                                                              \
     case 8: hipLaunchKernelGGL((KERNEL<scalar_t, LC, 8>), __VA_ARGS__); break; \

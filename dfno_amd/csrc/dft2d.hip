@@ -37,29 +37,17 @@
 #include <tuple>
 
 #include "kernels.h"
+#include "device_util.h"
 
 namespace {
+
+using namespace dfno_io;
 
 constexpr int kBlock = 256;
 constexpr int kMaxZ = 64;
 constexpr int kMaxT = 64;
 constexpr int kMaxMZ = 48;
 constexpr int kMaxMT = 32;
-
-__device__ __forceinline__ float zt_b2f(unsigned short h) {
-  return __uint_as_float(((unsigned int)h) << 16);
-}
-
-__device__ __forceinline__ unsigned short zt_f2b(float f) {
-  __hip_bfloat16 h = __float2bfloat16(f);
-  return *reinterpret_cast<unsigned short*>(&h);
-}
-
-template <typename TI>
-__device__ __forceinline__ float zt_ld(const TI* p) {
-  if constexpr (std::is_same<TI, unsigned short>::value) return zt_b2f(*p);
-  else return (float)*p;
-}
 
 // ---------------------------------------------------------------------------
 // zt_fwd: per plane, stage x [Z][T] in LDS, then
@@ -100,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void zt_fwd_kernel(
     // stage np planes
     for (int idx = threadIdx.x; idx < np * zt; idx += kBlock) {
       const int pl = idx / zt;
-      xs[pl * zt + (idx - pl * zt)] = zt_ld(in + (p0 + pl) * (long)zt +
+      xs[pl * zt + (idx - pl * zt)] = ld(in + (p0 + pl) * (long)zt +
                                             (idx - pl * zt));
     }
     __syncthreads();
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void zt_fwd_pin_kernel(
     const int np = (int)min((long)PLW, planes - p0);
     __syncthreads();
     for (int idx = threadIdx.x; idx < np * ZT; idx += kBlock)
-      xs[idx] = zt_ld(in + p0 * (long)ZT + idx);
+      xs[idx] = ld(in + p0 * (long)ZT + idx);
     __syncthreads();
     // stage 1: B[pl][z][kt] — rows as float2, twiddles from registers
     const int nrow = np * Z;
@@ -326,7 +314,7 @@ __global__ __launch_bounds__(kBlock) void zt_inv_kernel(
       }
       TO* dst = out + (p0 + pl) * (long)Z * T + r;
       if constexpr (std::is_same<TO, unsigned short>::value)
-        *dst = zt_f2b(acc0);
+        *dst = f2b(acc0);
       else
         *dst = (TO)acc0;
     }
@@ -432,7 +420,7 @@ __global__ __launch_bounds__(kBlock) void zt_inv_pin_kernel(
       for (int i = threadIdx.x; i < nrow * T; i += kBlock) {
         float v = stagebuf[i];
         if constexpr (std::is_same<TO, unsigned short>::value) {
-          reinterpret_cast<unsigned short*>(out)[gbase + i] = zt_f2b(v);
+          reinterpret_cast<unsigned short*>(out)[gbase + i] = f2b(v);
         } else {
           if (acc != nullptr) v += acc[gbase + i];
           out[gbase + i] = (TO)v;

@@ -137,7 +137,8 @@ at::Tensor dft_pad_irfft_bf16(const at::Tensor& y, int64_t dim, int64_t n_out,
 at::Tensor dft_rfft_trunc_adj_bf16(const at::Tensor& gy, int64_t dim,
                                    int64_t n, const at::Tensor& accum);
 
-// bf16-storage pointwise kernels (bf16.hip; fp32 arithmetic):
+// bf16-storage pointwise kernels (fp32 arithmetic; pointwise.hip, the
+// grad-W reduction in bf16.hip):
 std::vector<at::Tensor> bf16_channel_mix(const at::Tensor& x, const at::Tensor& W,
                                          const at::Tensor& b, bool act, bool wt,
                                          bool write_z, const at::Tensor& res);

@@ -17,8 +17,8 @@
 // write / gy read is a contiguous Tn-dword run; backward's gW2/gb2
 // reduce as v_mfma_f32_16x16x4 over per-wave LDS tiles (ones-column
 // trick for gb2) with fragments carried across pairs, and gW1/gb1
-// accumulate per-lane (k is fixed).  The chunked per-thread kernels
-// below them serve fp64/odd shapes.
+// accumulate per-lane (k is fixed).  fp64 (the gradient-check path) runs
+// the chunked general-lift kernels for every T_in, 1 included.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -27,258 +27,18 @@
 
 #include "kernels.h"
 #include "gelu_math.h"
+#include "device_util.h"
 
 namespace {
 
+using namespace dfno_io;
+
 constexpr int kBlock = 256;
-
-template <typename T>
-__device__ __forceinline__ T gelu_(T z) { return dfno_gelu::gelu(z); }
-
-template <typename T>
-__device__ __forceinline__ T gelu_g_(T z) { return dfno_gelu::gelu_grad(z); }
-
-__device__ __forceinline__ float lh_ld(const float* p) { return *p; }
-__device__ __forceinline__ float lh_ld(const unsigned short* p) {
-  return __uint_as_float(((unsigned int)*p) << 16);
-}
-__device__ __forceinline__ void lh_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void lh_st(unsigned short* p, float v) {
-  __hip_bfloat16 h = __float2bfloat16(v);
-  *p = *reinterpret_cast<unsigned short*>(&h);
-}
-
-template <typename T>
-__device__ __forceinline__ T lh_wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// x: [B, C, S] (T_in == 1 folded away), out: [B, W, S, T]
-// W1: [T, 1], b1: [T], W2: [W, C], b2: [W]
-//
-// Both kernels chunk the time axis (KC columns at a time): the first cut
-// held h/z1/gh[CCAP][TCAP] per thread (384 floats -> 256 VGPRs + ~600
-// spilled, 1 wave/SIMD, every element round-tripping scratch).  Chunked,
-// the live set is ~2*CCAP*KC + temps and z1 is recomputed (2 FMA) where
-// its gradient factor is needed.
-template <typename T, int CCAP, int TCAP, int WCAP, int WT = 0>
-__global__ __launch_bounds__(kBlock, 3) void lift_head_fwd_kernel(
-    const T* __restrict__ x, const T* __restrict__ W1, const T* __restrict__ b1,
-    const T* __restrict__ W2, const T* __restrict__ b2, T* __restrict__ out,
-    int B, int C, int W, int Tn, long S) {
-  constexpr int KC = 10;
-  __shared__ T w1[TCAP], bb1[TCAP], w2[WCAP * CCAP], bb2[WCAP];
-  for (int k = threadIdx.x; k < Tn; k += kBlock) { w1[k] = W1[k]; bb1[k] = b1[k]; }
-  for (int k = threadIdx.x; k < W * C; k += kBlock) w2[k] = W2[k];
-  for (int k = threadIdx.x; k < W; k += kBlock) bb2[k] = b2[k];
-  __syncthreads();
-
-  long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long t = t0; t < (long)B * S; t += stride) {
-    long b = t / S;
-    long s = t % S;
-
-    T xv[CCAP];
-#pragma unroll
-    for (int c = 0; c < CCAP; ++c)
-      if (c < C) xv[c] = x[(b * C + c) * S + s];
-
-    for (int k0 = 0; k0 < Tn; k0 += KC) {
-      const int kn = min(KC, Tn - k0);
-      // h[c][k] = gelu(W1[k] * x[c] + b1[k]) for this chunk
-      T h[CCAP][KC];
-#pragma unroll
-      for (int c = 0; c < CCAP; ++c) {
-        if (c < C) {
-#pragma unroll
-          for (int k = 0; k < KC; ++k)
-            if (k < kn) h[c][k] = gelu_(w1[k0 + k] * xv[c] + bb1[k0 + k]);
-        }
-      }
-#pragma unroll 4
-      for (int w = 0; w < (WT > 0 ? WT : 512); ++w) {
-        if (WT == 0 && w >= W) break;
-        T acc[KC];
-#pragma unroll
-        for (int k = 0; k < KC; ++k)
-          if (k < kn) acc[k] = bb2[w];
-#pragma unroll
-        for (int c = 0; c < CCAP; ++c) {
-          if (c < C) {
-            T wv = w2[(size_t)w * C + c];
-#pragma unroll
-            for (int k = 0; k < KC; ++k)
-              if (k < kn) acc[k] += wv * h[c][k];
-          }
-        }
-        T* dst = out + ((b * W + w) * S + s) * Tn + k0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k)
-          if (k < kn) dst[k] = gelu_(acc[k]);
-      }
-    }
-  }
-}
-
-// gy: [B, W, S, T]; outputs gx [B, C, S] and gW1/gb1/gW2/gb2 via atomics.
-template <typename T, int CCAP, int TCAP, int WCAP, int WT = 0>
-__global__ __launch_bounds__(kBlock, 3) void lift_head_bwd_kernel(
-    const T* __restrict__ gy, const T* __restrict__ x,
-    const T* __restrict__ W1, const T* __restrict__ b1,
-    const T* __restrict__ W2, const T* __restrict__ b2,
-    T* __restrict__ gx, T* __restrict__ gW1, T* __restrict__ gb1,
-    T* __restrict__ gW2, T* __restrict__ gb2,
-    int B, int C, int W, int Tn, long S) {
-  constexpr int KC = 10;
-  __shared__ T w1[TCAP], bb1[TCAP], w2[WCAP * CCAP], bb2[WCAP];
-  // per-wave partial accumulators
-  __shared__ T a_gW1[4][TCAP], a_gb1[4][TCAP], a_gW2[4][WCAP * CCAP], a_gb2[4][WCAP];
-  for (int k = threadIdx.x; k < Tn; k += kBlock) { w1[k] = W1[k]; bb1[k] = b1[k]; }
-  for (int k = threadIdx.x; k < W * C; k += kBlock) w2[k] = W2[k];
-  for (int k = threadIdx.x; k < W; k += kBlock) bb2[k] = b2[k];
-  for (int k = threadIdx.x; k < 4 * TCAP; k += kBlock)
-    a_gW1[k / TCAP][k % TCAP] = a_gb1[k / TCAP][k % TCAP] = T(0);
-  for (int k = threadIdx.x; k < 4 * WCAP * CCAP; k += kBlock)
-    a_gW2[k / (WCAP * CCAP)][k % (WCAP * CCAP)] = T(0);
-  for (int k = threadIdx.x; k < 4 * WCAP; k += kBlock)
-    a_gb2[k / WCAP][k % WCAP] = T(0);
-  __syncthreads();
-
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-
-  long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long t = t0; t < (long)B * S; t += stride) {
-    long b = t / S;
-    long s = t % S;
-
-    T xv[CCAP], gxa[CCAP];
-#pragma unroll
-    for (int c = 0; c < CCAP; ++c) {
-      if (c < C) {
-        xv[c] = x[(b * C + c) * S + s];
-        gxa[c] = T(0);
-      }
-    }
-
-    for (int k0 = 0; k0 < Tn; k0 += KC) {
-      const int kn = min(KC, Tn - k0);
-      T h[CCAP][KC], gh[CCAP][KC];
-#pragma unroll
-      for (int c = 0; c < CCAP; ++c) {
-        if (c < C) {
-#pragma unroll
-          for (int k = 0; k < KC; ++k) {
-            if (k < kn) {
-              h[c][k] = gelu_(w1[k0 + k] * xv[c] + bb1[k0 + k]);
-              gh[c][k] = T(0);
-            }
-          }
-        }
-      }
-
-#pragma unroll 4
-      for (int w = 0; w < (WT > 0 ? WT : 512); ++w) {
-        if (WT == 0 && w >= W) break;
-        const T* gyp = gy + ((b * W + w) * S + s) * Tn + k0;
-        T gz2[KC];
-        T gb2p = T(0);
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-          if (k < kn) {
-            // recompute z2[w][k]
-            T z2 = bb2[w];
-#pragma unroll
-            for (int c = 0; c < CCAP; ++c)
-              if (c < C) z2 += w2[(size_t)w * C + c] * h[c][k];
-            gz2[k] = gyp[k] * gelu_g_(z2);
-            gb2p += gz2[k];
-          }
-        }
-        // accumulate gh and wave-reduced gW2 partials
-#pragma unroll
-        for (int c = 0; c < CCAP; ++c) {
-          if (c < C) {
-            T wv = w2[(size_t)w * C + c];
-            T gw2p = T(0);
-#pragma unroll
-            for (int k = 0; k < KC; ++k) {
-              if (k < kn) {
-                gh[c][k] += wv * gz2[k];
-                gw2p += gz2[k] * h[c][k];
-              }
-            }
-            gw2p = lh_wave_sum(gw2p);
-            if (lane == 0) a_gW2[wave][w * C + c] += gw2p;
-          }
-        }
-        gb2p = lh_wave_sum(gb2p);
-        if (lane == 0) a_gb2[wave][w] += gb2p;
-      }
-
-      // gz1 = gh * gelu'(z1); gx[c] += sum_k W1[k] gz1[c][k];
-      // gW1[k] += sum_c gz1[c][k] * x[c]; gb1[k] += sum_c gz1[c][k]
-#pragma unroll
-      for (int c = 0; c < CCAP; ++c) {
-        if (c < C) {
-#pragma unroll
-          for (int k = 0; k < KC; ++k) {
-            if (k < kn) {
-              T gz1 = gh[c][k] * gelu_g_(w1[k0 + k] * xv[c] + bb1[k0 + k]);
-              gh[c][k] = gz1;  // reuse as gz1 for the reductions below
-              gxa[c] += w1[k0 + k] * gz1;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < KC; ++k) {
-        if (k < kn) {
-          T pw = T(0), pb = T(0);
-#pragma unroll
-          for (int c = 0; c < CCAP; ++c) {
-            if (c < C) {
-              pw += gh[c][k] * xv[c];
-              pb += gh[c][k];
-            }
-          }
-          pw = lh_wave_sum(pw);
-          pb = lh_wave_sum(pb);
-          if (lane == 0) { a_gW1[wave][k0 + k] += pw; a_gb1[wave][k0 + k] += pb; }
-        }
-      }
-    }
-
-#pragma unroll
-    for (int c = 0; c < CCAP; ++c)
-      if (c < C) gx[(b * C + c) * S + s] = gxa[c];
-  }
-
-  __syncthreads();
-  for (int k = threadIdx.x; k < Tn; k += kBlock) {
-    T v = a_gW1[0][k] + a_gW1[1][k] + a_gW1[2][k] + a_gW1[3][k];
-    if (v != T(0)) atomicAdd(&gW1[k], v);
-    v = a_gb1[0][k] + a_gb1[1][k] + a_gb1[2][k] + a_gb1[3][k];
-    if (v != T(0)) atomicAdd(&gb1[k], v);
-  }
-  for (int k = threadIdx.x; k < W * C; k += kBlock) {
-    T v = a_gW2[0][k] + a_gW2[1][k] + a_gW2[2][k] + a_gW2[3][k];
-    if (v != T(0)) atomicAdd(&gW2[k], v);
-  }
-  for (int k = threadIdx.x; k < W; k += kBlock) {
-    T v = a_gb2[0][k] + a_gb2[1][k] + a_gb2[2][k] + a_gb2[3][k];
-    if (v != T(0)) atomicAdd(&gb2[k], v);
-  }
-}
 
 // fp32 lane-per-k variants: each 64-lane wave covers TWO s-points with
 // lanes 0..Tn-1 / 32..32+Tn-1 owning one time column each, so every gy
-// read and out write is a contiguous Tn-dword run (the per-thread layout
-// above streams 30-float runs per lane -> fully scattered wave accesses;
+// read and out write is a contiguous Tn-dword run (a one-point-per-thread
+// layout streams 30-float runs per lane -> fully scattered wave accesses;
 // measured 699/843 us vs ~110/130 us of traffic).  Per-lane state is
 // ~40 VGPRs; gW1/gb1 partials accumulate in registers (k fixed per lane).
 template <int WT, typename TIO = float>
@@ -311,8 +71,8 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_lk_kernel(
 #pragma unroll
     for (int c = 0; c < CC; ++c) {
       if (c < C) {
-        const float xv = ev ? lh_ld(x + (b * C + c) * S + s) : 0.f;
-        h[c] = kv ? gelu_(w1[k] * xv + bb1[k]) : 0.f;
+        const float xv = ev ? ld(x + (b * C + c) * S + s) : 0.f;
+        h[c] = kv ? dfno_gelu::gelu(w1[k] * xv + bb1[k]) : 0.f;
       }
     }
 #pragma unroll 4
@@ -323,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_lk_kernel(
       for (int c = 0; c < CC; ++c)
         if (c < C) acc += w2[w * C + c] * h[c];
       if (ev && kv)
-        lh_st(out + ((b * W + w) * S + s) * Tn + k, gelu_(acc));
+        st(out + ((b * W + w) * S + s) * Tn + k, dfno_gelu::gelu(acc));
     }
   }
 }
@@ -380,8 +140,8 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
 #pragma unroll
     for (int c = 0; c < CC; ++c) {
       if (c < C) {
-        xv[c] = ev ? lh_ld(x + (b * C + c) * S + s) : 0.f;
-        h[c] = kv ? gelu_(w1[k] * xv[c] + bb1[k]) : 0.f;
+        xv[c] = ev ? ld(x + (b * C + c) * S + s) : 0.f;
+        h[c] = kv ? dfno_gelu::gelu(w1[k] * xv[c] + bb1[k]) : 0.f;
         gh[c] = 0.f;
         hw[c * GLD + lane] = h[c];
       }
@@ -393,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
 #pragma unroll
     for (int w = 0; w < (WT > 0 ? WT : 24); ++w) {
       gyv[w] = (w < W && ev && kv)
-                   ? lh_ld(gy + ((b * W + w) * S + s) * Tn + k) : 0.f;
+                   ? ld(gy + ((b * W + w) * S + s) * Tn + k) : 0.f;
     }
 #pragma unroll 4
     for (int w = 0; w < (WT > 0 ? WT : 512); ++w) {
@@ -402,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
 #pragma unroll
       for (int c = 0; c < CC; ++c)
         if (c < C) z2 += w2[w * C + c] * h[c];
-      const float gz2 = gyv[w] * gelu_g_(z2);
+      const float gz2 = gyv[w] * dfno_gelu::gelu_grad(z2);
       gzw[w * GLD + lane] = gz2;
 #pragma unroll
       for (int c = 0; c < CC; ++c)
@@ -428,14 +188,14 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
 #pragma unroll
     for (int c = 0; c < CC; ++c) {
       if (c < C) {
-        const float gz1 = kv ? gh[c] * gelu_g_(w1[k] * xv[c] + bb1[k]) : 0.f;
+        const float gz1 = kv ? gh[c] * dfno_gelu::gelu_grad(w1[k] * xv[c] + bb1[k]) : 0.f;
         pgW1 += gz1 * xv[c];
         pgb1 += gz1;
         float gxa = kv ? w1[k] * gz1 : 0.f;
 #pragma unroll
         for (int off = 16; off > 0; off >>= 1)
           gxa += __shfl_xor(gxa, off, 64);
-        if (ev && k == 0) lh_st(gx + (b * C + c) * S + s, gxa);
+        if (ev && k == 0) st(gx + (b * C + c) * S + s, gxa);
       }
     }
   }
@@ -492,8 +252,8 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
   constexpr int NPASS = (XT + 63) / 64;
   __shared__ float w2[24 * CC], bb2[24];
   __shared__ float xt[kBlock / 64][XT];
-  for (int j = threadIdx.x; j < W * C; j += kBlock) w2[j] = lh_ld(W2 + j);
-  for (int j = threadIdx.x; j < W; j += kBlock) bb2[j] = lh_ld(b2 + j);
+  for (int j = threadIdx.x; j < W * C; j += kBlock) w2[j] = ld(W2 + j);
+  for (int j = threadIdx.x; j < W; j += kBlock) bb2[j] = ld(b2 + j);
   for (int j = threadIdx.x; j < (kBlock / 64) * XT; j += kBlock)
     (&xt[0][0])[j] = 0.f;
   __syncthreads();
@@ -508,8 +268,8 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
   float w1r[TIC];
 #pragma unroll
   for (int i = 0; i < TIC; ++i)
-    w1r[i] = (kv && i < Ti) ? lh_ld(W1 + k * Ti + i) : 0.f;
-  const float b1k = kv ? lh_ld(b1 + k) : 0.f;
+    w1r[i] = (kv && i < Ti) ? ld(W1 + k * Ti + i) : 0.f;
+  const float b1k = kv ? ld(b1 + k) : 0.f;
 
   // staging roles: lane (+64 per pass) <-> (point, channel, step) of the tile
   int sp[NPASS], sc[NPASS], si[NPASS];
@@ -530,7 +290,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
     if (!sv[j] || t >= nwork || e >= N) return 0.f;
     const int b = e / S;
     const int s = e - b * S;
-    return lh_ld(x + ((long)(b * C + sc[j]) * S + s) * Ti + si[j]);
+    return ld(x + ((long)(b * C + sc[j]) * S + s) * Ti + si[j]);
   };
 
   const int t0 = (int)blockIdx.x * (kBlock / 64) + wave;
@@ -557,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
         float z = b1k;
 #pragma unroll
         for (int i = 0; i < TIC; ++i) z += w1r[i] * xw[(p * CC + c) * TIC + i];
-        h[c] = kv ? gelu_(z) : 0.f;
+        h[c] = kv ? dfno_gelu::gelu(z) : 0.f;
       }
     }
     lh_wave_sync();                           // tile reads done before refill
@@ -569,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
       for (int c = 0; c < CC; ++c)
         if (c < C) acc += w2[w * C + c] * h[c];
       if (ev && kv)
-        lh_st(out + ((long)(b * W + w) * S + s) * To + k, gelu_(acc));
+        st(out + ((long)(b * W + w) * S + s) * To + k, dfno_gelu::gelu(acc));
     }
   }
 }
@@ -602,9 +362,9 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
   __shared__ float gzt[NW][24 * GLD];
   __shared__ float ht[NW][CC * GLD];
   __shared__ float xt[NW][XT];
-  for (int j = threadIdx.x; j < To * Ti; j += kBlock) w1s[j] = lh_ld(W1 + j);
-  for (int j = threadIdx.x; j < W * C; j += kBlock) w2[j] = lh_ld(W2 + j);
-  for (int j = threadIdx.x; j < W; j += kBlock) bb2[j] = lh_ld(b2 + j);
+  for (int j = threadIdx.x; j < To * Ti; j += kBlock) w1s[j] = ld(W1 + j);
+  for (int j = threadIdx.x; j < W * C; j += kBlock) w2[j] = ld(W2 + j);
+  for (int j = threadIdx.x; j < W; j += kBlock) bb2[j] = ld(b2 + j);
   for (int j = threadIdx.x; j < NW * XT; j += kBlock) (&xt[0][0])[j] = 0.f;
   __syncthreads();
 
@@ -622,10 +382,10 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
   float w1r[TIC], pgW1[TIC];
 #pragma unroll
   for (int i = 0; i < TIC; ++i) {
-    w1r[i] = (kv && i < Ti) ? lh_ld(W1 + k * Ti + i) : 0.f;
+    w1r[i] = (kv && i < Ti) ? ld(W1 + k * Ti + i) : 0.f;
     pgW1[i] = 0.f;
   }
-  const float b1k = kv ? lh_ld(b1 + k) : 0.f;
+  const float b1k = kv ? ld(b1 + k) : 0.f;
   float pgb1 = 0.f;
   f32x4_lh wacc[2];                           // gW2/gb2 frags (2 m-tiles)
   wacc[0] = f32x4_lh{0.f, 0.f, 0.f, 0.f};
@@ -660,7 +420,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 #pragma unroll
   for (int j = 0; j < NPASS; ++j) {
     const long o = xoff(t0, j);
-    xn[j] = o >= 0 ? lh_ld(x + o) : 0.f;
+    xn[j] = o >= 0 ? ld(x + o) : 0.f;
   }
   for (int t = t0; t < nwork; t += stride) {
     long xo[NPASS];                           // this iteration's gx targets
@@ -673,7 +433,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 #pragma unroll
     for (int j = 0; j < NPASS; ++j) {
       const long o = xoff(t + stride, j);
-      xn[j] = o >= 0 ? lh_ld(x + o) : 0.f;
+      xn[j] = o >= 0 ? ld(x + o) : 0.f;
     }
 
     const int e = PW * t + p;
@@ -685,7 +445,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 #pragma unroll
     for (int w = 0; w < (WT > 0 ? WT : 24); ++w) {
       gyv[w] = (w < W && ev && kv)
-                   ? lh_ld(gy + ((long)(b * W + w) * S + s) * To + k) : 0.f;
+                   ? ld(gy + ((long)(b * W + w) * S + s) * To + k) : 0.f;
     }
     float z1[CC], h[CC], gh[CC];
 #pragma unroll
@@ -695,7 +455,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 #pragma unroll
         for (int i = 0; i < TIC; ++i) z += w1r[i] * xw[(p * CC + c) * TIC + i];
         z1[c] = z;
-        h[c] = kv ? gelu_(z) : 0.f;
+        h[c] = kv ? dfno_gelu::gelu(z) : 0.f;
         gh[c] = 0.f;
         hw[c * GLD + lane] = h[c];
       }
@@ -707,7 +467,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 #pragma unroll
       for (int c = 0; c < CC; ++c)
         if (c < C) z2 += w2[w * C + c] * h[c];
-      const float gz2 = gyv[w] * gelu_g_(z2);
+      const float gz2 = gyv[w] * dfno_gelu::gelu_grad(z2);
       gzw[w * GLD + lane] = gz2;
 #pragma unroll
       for (int c = 0; c < CC; ++c)
@@ -734,7 +494,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 #pragma unroll
     for (int c = 0; c < CC; ++c) {
       if (c < C) {
-        const float gz1 = kv ? gh[c] * gelu_g_(z1[c]) : 0.f;
+        const float gz1 = kv ? gh[c] * dfno_gelu::gelu_grad(z1[c]) : 0.f;
         pgb1 += gz1;
 #pragma unroll
         for (int i = 0; i < TIC; ++i)
@@ -758,7 +518,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
           a3 += wc[(kk + 3) * Ti] * g1[kk + 3];
         }
         for (; kk < To; ++kk) a0 += wc[kk * Ti] * g1[kk];
-        lh_st(gx + xo[j], (a0 + a1) + (a2 + a3));
+        st(gx + xo[j], (a0 + a1) + (a2 + a3));
       }
     }
     lh_wave_sync();                           // tiles free for the next point
@@ -837,7 +597,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_chunk_kernel(
             if (kk < kn) {
               T z = bb1[k0 + kk];
               for (int i = 0; i < Ti; ++i) z += w1[(k0 + kk) * Ti + i] * xp[i];
-              h[c][kk] = gelu_(z);
+              h[c][kk] = dfno_gelu::gelu(z);
             }
           }
         }
@@ -851,7 +611,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_chunk_kernel(
 #pragma unroll
             for (int c = 0; c < CC; ++c)
               if (c < C) acc += w2[w * C + c] * h[c][kk];
-            dst[kk] = gelu_(acc);
+            dst[kk] = dfno_gelu::gelu(acc);
           }
         }
       }
@@ -899,7 +659,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
               T z = bb1[k0 + kk];
               for (int i = 0; i < Ti; ++i) z += w1[(k0 + kk) * Ti + i] * xp[i];
               z1[c][kk] = z;
-              h[c][kk] = gelu_(z);
+              h[c][kk] = dfno_gelu::gelu(z);
               gh[c][kk] = T(0);
             }
           }
@@ -916,7 +676,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
 #pragma unroll
             for (int c = 0; c < CC; ++c)
               if (c < C) z2 += w2[w * C + c] * h[c][kk];
-            gz2[kk] = ev ? gyp[kk] * gelu_g_(z2) : T(0);
+            gz2[kk] = ev ? gyp[kk] * dfno_gelu::gelu_grad(z2) : T(0);
             gb2p += gz2[kk];
           }
         }
@@ -932,11 +692,11 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
                 gw2p += gz2[kk] * h[c][kk];
               }
             }
-            gw2p = lh_wave_sum(gw2p);
+            gw2p = wave_sum(gw2p);
             if (lane == 0) atomicAdd(&a_gW2[w * C + c], gw2p);
           }
         }
-        gb2p = lh_wave_sum(gb2p);
+        gb2p = wave_sum(gb2p);
         if (lane == 0) atomicAdd(&a_gb2[w], gb2p);
       }
       // gz1 = gh * gelu'(z1) (kept in gh); gx/gW1/gb1 from it
@@ -945,7 +705,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
         if (c < C) {
 #pragma unroll
           for (int kk = 0; kk < KC; ++kk)
-            if (kk < kn) gh[c][kk] *= gelu_g_(z1[c][kk]);
+            if (kk < kn) gh[c][kk] *= dfno_gelu::gelu_grad(z1[c][kk]);
           if (ev) {
             T* gxp = gx + ((long)(b * C + c) * S + s) * Ti;
             for (int i = 0; i < Ti; ++i) {
@@ -965,7 +725,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
 #pragma unroll
           for (int c = 0; c < CC; ++c)
             if (c < C) pb += gh[c][kk];
-          pb = lh_wave_sum(pb);
+          pb = wave_sum(pb);
           if (lane == 0) atomicAdd(&a_gb1[k0 + kk], pb);
           for (int i = 0; i < Ti; ++i) {
             T pw = T(0);
@@ -973,7 +733,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
             for (int c = 0; c < CC; ++c)
               if (c < C)
                 pw += gh[c][kk] * x[((long)(b * C + c) * S + s) * Ti + i];
-            pw = lh_wave_sum(pw);
+            pw = wave_sum(pw);
             if (lane == 0) atomicAdd(&a_gW1[(k0 + kk) * Ti + i], pw);
           }
         }
@@ -990,21 +750,6 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
     if (a_gW2[j] != T(0)) atomicAdd(&gW2[j], a_gW2[j]);
   for (int j = threadIdx.x; j < W; j += kBlock)
     if (a_gb2[j] != T(0)) atomicAdd(&gb2[j], a_gb2[j]);
-}
-
-int grid_for_l(long work) {
-  long g = (work + kBlock - 1) / kBlock;
-  long cap = 256L * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-void check_lf(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kDouble,
-              name, " must be float32/float64");
 }
 
 // ---- host side of the general lift: x [B, C, S, Ti] ----
@@ -1042,10 +787,7 @@ LiftDims lift_gen_dims(const at::Tensor& x, const at::Tensor& W1,
 int lift_gen_grid(const LiftDims& d, int lp, long cap) {
   const long pw = 64 / lp;
   const long nwork = (d.N + pw - 1) / pw;
-  long g = (nwork + kBlock / 64 - 1) / (kBlock / 64);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
+  return launch_grid(nwork, kBlock / 64, cap);
 }
 
 // LP x TIC x WT dispatch shared by forward and backward
@@ -1076,7 +818,8 @@ at::Tensor lift_head_gen_fwd(const at::Tensor& x, const at::Tensor& W1,
   auto W2f = W2.contiguous(), b2f = b2.contiguous();
   if (x.scalar_type() == at::kDouble) {
     hipLaunchKernelGGL((lift_head_fwd_gen_chunk_kernel<double>),
-                       dim3(grid_for_l(d.N)), dim3(kBlock), 0, stream,
+                       dim3(launch_grid(d.N, kBlock, 256L * 8)), dim3(kBlock), 0,
+                       stream,
                        x.data_ptr<double>(), W1f.data_ptr<double>(),
                        b1f.data_ptr<double>(), W2f.data_ptr<double>(),
                        b2f.data_ptr<double>(), out.data_ptr<double>(),
@@ -1126,7 +869,8 @@ std::vector<at::Tensor> lift_head_gen_bwd(
   auto W2f = W2.contiguous(), b2f = b2.contiguous();
   if (x.scalar_type() == at::kDouble) {
     hipLaunchKernelGGL((lift_head_bwd_gen_chunk_kernel<double>),
-                       dim3(grid_for_l(d.N)), dim3(kBlock), 0, stream,
+                       dim3(launch_grid(d.N, kBlock, 256L * 8)), dim3(kBlock), 0,
+                       stream,
                        gy.data_ptr<double>(), x.data_ptr<double>(),
                        W1f.data_ptr<double>(), b1f.data_ptr<double>(),
                        W2f.data_ptr<double>(), b2f.data_ptr<double>(),
@@ -1169,54 +913,38 @@ at::Tensor lift_head_fwd(const at::Tensor& x, const at::Tensor& W1,
                          const at::Tensor& b2) {
   if (x.dim() == 4) return lift_head_gen_fwd(x, W1, b1, W2, b2);
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "x must be contiguous GPU");
-  if (x.scalar_type() != at::kBFloat16) { check_lf(x, "x"); }
+  if (x.scalar_type() != at::kBFloat16) { check_real(x, "x"); }
   TORCH_CHECK(x.dim() == 3, "x must be [B,C,S] or [B,C,S,Ti]");
   int B = (int)x.size(0), C = (int)x.size(1);
   long S = x.size(2);
   int Tn = (int)W1.size(0), W = (int)W2.size(0);
   TORCH_CHECK(W1.size(1) == 1 && (int)W2.size(1) == C, "lift_head shapes");
   TORCH_CHECK(C <= 4 && Tn <= 32 && W <= 24, "lift_head: unsupported dims");
+  // fp64 (the gradient-check path) has no lane-per-k kernel: [B,C,S] runs
+  // the chunked general lift as [B,C,S,1]
+  if (x.scalar_type() == at::kDouble)
+    return lift_head_gen_fwd(x.unsqueeze(-1), W1, b1, W2, b2);
 
   auto out = at::empty({B, W, S, (long)Tn}, x.options());
   if (x.numel() == 0) return out;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = grid_for_l((long)B * S);
-  if (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16) {
-    int grid2 = grid_for_l(2 * (((long)B * S + 1) / 2) * 32);
-    const bool bf16 = x.scalar_type() == at::kBFloat16;
-    auto W1f = bf16 ? W1.to(at::kFloat).contiguous() : W1;
-    auto b1f = bf16 ? b1.to(at::kFloat).contiguous() : b1;
-    auto W2f = bf16 ? W2.to(at::kFloat).contiguous() : W2;
-    auto b2f = bf16 ? b2.to(at::kFloat).contiguous() : b2;
+  int grid2 = launch_grid(2 * (((long)B * S + 1) / 2) * 32, kBlock, 256L * 8);
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  auto W1f = bf16 ? W1.to(at::kFloat).contiguous() : W1;
+  auto b1f = bf16 ? b1.to(at::kFloat).contiguous() : b1;
+  auto W2f = bf16 ? W2.to(at::kFloat).contiguous() : W2;
+  auto b2f = bf16 ? b2.to(at::kFloat).contiguous() : b2;
 #define LH_FWD(WT, TIO)                                                       \
-    hipLaunchKernelGGL((lift_head_fwd_lk_kernel<WT, TIO>), dim3(grid2),       \
-                       dim3(kBlock), 0, stream,                               \
-                       reinterpret_cast<const TIO*>(x.data_ptr()),            \
-                       W1f.data_ptr<float>(), b1f.data_ptr<float>(),          \
-                       W2f.data_ptr<float>(), b2f.data_ptr<float>(),          \
-                       reinterpret_cast<TIO*>(out.data_ptr()), B, C, W, Tn, S)
-    if (bf16) { if (W == 20) LH_FWD(20, unsigned short);
-                else LH_FWD(0, unsigned short); }
-    else { if (W == 20) LH_FWD(20, float); else LH_FWD(0, float); }
+  hipLaunchKernelGGL((lift_head_fwd_lk_kernel<WT, TIO>), dim3(grid2),         \
+                     dim3(kBlock), 0, stream,                                 \
+                     reinterpret_cast<const TIO*>(x.data_ptr()),              \
+                     W1f.data_ptr<float>(), b1f.data_ptr<float>(),            \
+                     W2f.data_ptr<float>(), b2f.data_ptr<float>(),            \
+                     reinterpret_cast<TIO*>(out.data_ptr()), B, C, W, Tn, S)
+  if (bf16) { if (W == 20) LH_FWD(20, unsigned short);
+              else LH_FWD(0, unsigned short); }
+  else { if (W == 20) LH_FWD(20, float); else LH_FWD(0, float); }
 #undef LH_FWD
-    DFNO_CHECK_LAUNCH("lift_head");
-    return out;
-  }
-  AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "lift_head_fwd", [&] {
-    if (W == 20) {
-      hipLaunchKernelGGL((lift_head_fwd_kernel<scalar_t, 4, 32, 24, 20>), dim3(grid),
-                         dim3(kBlock), 0, stream, x.data_ptr<scalar_t>(),
-                         W1.data_ptr<scalar_t>(), b1.data_ptr<scalar_t>(),
-                         W2.data_ptr<scalar_t>(), b2.data_ptr<scalar_t>(),
-                         out.data_ptr<scalar_t>(), B, C, W, Tn, S);
-    } else {
-      hipLaunchKernelGGL((lift_head_fwd_kernel<scalar_t, 4, 32, 24>), dim3(grid),
-                         dim3(kBlock), 0, stream, x.data_ptr<scalar_t>(),
-                         W1.data_ptr<scalar_t>(), b1.data_ptr<scalar_t>(),
-                         W2.data_ptr<scalar_t>(), b2.data_ptr<scalar_t>(),
-                         out.data_ptr<scalar_t>(), B, C, W, Tn, S);
-    }
-  });
   DFNO_CHECK_LAUNCH("lift_head");
   return out;
 }
@@ -1227,16 +955,20 @@ std::vector<at::Tensor> lift_head_bwd(const at::Tensor& gy, const at::Tensor& x,
   TORCH_CHECK(gy.is_cuda() && gy.is_contiguous() && x.is_contiguous() &&
               gy.scalar_type() == x.scalar_type(), "lift_head_bwd IO");
   if (x.dim() == 4) return lift_head_gen_bwd(gy, x, W1, b1, W2, b2);
-  if (x.scalar_type() != at::kBFloat16) { check_lf(gy, "gy"); check_lf(x, "x"); }
+  if (x.scalar_type() != at::kBFloat16) { check_real(gy, "gy"); check_real(x, "x"); }
   int B = (int)x.size(0), C = (int)x.size(1);
   long S = x.size(2);
   int Tn = (int)W1.size(0), W = (int)W2.size(0);
   TORCH_CHECK(C <= 4 && Tn <= 32 && W <= 24, "lift_head: unsupported dims");
+  if (x.scalar_type() == at::kDouble) {   // as in lift_head_fwd
+    auto g = lift_head_gen_bwd(gy, x.unsqueeze(-1), W1, b1, W2, b2);
+    g[0] = g[0].view(x.sizes());
+    return g;
+  }
 
   auto gx = at::empty_like(x);
   // weight grads accumulate fp32 even for bf16 activations
-  auto fopt = x.options().dtype(x.scalar_type() == at::kDouble
-                                    ? at::kDouble : at::kFloat);
+  auto fopt = x.options().dtype(at::kFloat);
   auto gW1 = at::zeros({Tn, 1}, fopt);
   auto gb1 = at::zeros({Tn}, fopt);
   auto gW2 = at::zeros({W, C}, fopt);
@@ -1244,53 +976,27 @@ std::vector<at::Tensor> lift_head_bwd(const at::Tensor& gy, const at::Tensor& x,
   if (x.numel() == 0) return {gx, gW1, gb1, gW2, gb2};
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = grid_for_l((long)B * S);
-  if (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16) {
-    int grid2 = grid_for_l(2 * (((long)B * S + 1) / 2) * 32);
-    const bool bf16 = x.scalar_type() == at::kBFloat16;
-    auto W1f = bf16 ? W1.to(at::kFloat).contiguous() : W1;
-    auto b1f = bf16 ? b1.to(at::kFloat).contiguous() : b1;
-    auto W2f = bf16 ? W2.to(at::kFloat).contiguous() : W2;
-    auto b2f = bf16 ? b2.to(at::kFloat).contiguous() : b2;
+  int grid2 = launch_grid(2 * (((long)B * S + 1) / 2) * 32, kBlock, 256L * 8);
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
+  auto W1f = bf16 ? W1.to(at::kFloat).contiguous() : W1;
+  auto b1f = bf16 ? b1.to(at::kFloat).contiguous() : b1;
+  auto W2f = bf16 ? W2.to(at::kFloat).contiguous() : W2;
+  auto b2f = bf16 ? b2.to(at::kFloat).contiguous() : b2;
 #define LH_BWD(WT, TIO)                                                       \
-    hipLaunchKernelGGL((lift_head_bwd_lk_kernel<WT, TIO>), dim3(grid2),       \
-                       dim3(kBlock), 0, stream,                               \
-                       reinterpret_cast<const TIO*>(gy.data_ptr()),           \
-                       reinterpret_cast<const TIO*>(x.data_ptr()),            \
-                       W1f.data_ptr<float>(), b1f.data_ptr<float>(),          \
-                       W2f.data_ptr<float>(), b2f.data_ptr<float>(),          \
-                       reinterpret_cast<TIO*>(gx.data_ptr()),                 \
-                       gW1.data_ptr<float>(), gb1.data_ptr<float>(),          \
-                       gW2.data_ptr<float>(), gb2.data_ptr<float>(),          \
-                       B, C, W, Tn, S)
-    if (bf16) { if (W == 20) LH_BWD(20, unsigned short);
-                else LH_BWD(0, unsigned short); }
-    else { if (W == 20) LH_BWD(20, float); else LH_BWD(0, float); }
+  hipLaunchKernelGGL((lift_head_bwd_lk_kernel<WT, TIO>), dim3(grid2),         \
+                     dim3(kBlock), 0, stream,                                 \
+                     reinterpret_cast<const TIO*>(gy.data_ptr()),             \
+                     reinterpret_cast<const TIO*>(x.data_ptr()),              \
+                     W1f.data_ptr<float>(), b1f.data_ptr<float>(),            \
+                     W2f.data_ptr<float>(), b2f.data_ptr<float>(),            \
+                     reinterpret_cast<TIO*>(gx.data_ptr()),                   \
+                     gW1.data_ptr<float>(), gb1.data_ptr<float>(),            \
+                     gW2.data_ptr<float>(), gb2.data_ptr<float>(),            \
+                     B, C, W, Tn, S)
+  if (bf16) { if (W == 20) LH_BWD(20, unsigned short);
+              else LH_BWD(0, unsigned short); }
+  else { if (W == 20) LH_BWD(20, float); else LH_BWD(0, float); }
 #undef LH_BWD
-    DFNO_CHECK_LAUNCH("lift_head");
-    return {gx, gW1, gb1, gW2, gb2};
-  }
-  AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "lift_head_bwd", [&] {
-    if (W == 20) {
-      hipLaunchKernelGGL((lift_head_bwd_kernel<scalar_t, 4, 32, 24, 20>), dim3(grid),
-                         dim3(kBlock), 0, stream, gy.data_ptr<scalar_t>(),
-                         x.data_ptr<scalar_t>(), W1.data_ptr<scalar_t>(),
-                         b1.data_ptr<scalar_t>(), W2.data_ptr<scalar_t>(),
-                         b2.data_ptr<scalar_t>(), gx.data_ptr<scalar_t>(),
-                         gW1.data_ptr<scalar_t>(), gb1.data_ptr<scalar_t>(),
-                         gW2.data_ptr<scalar_t>(), gb2.data_ptr<scalar_t>(),
-                         B, C, W, Tn, S);
-    } else {
-      hipLaunchKernelGGL((lift_head_bwd_kernel<scalar_t, 4, 32, 24>), dim3(grid),
-                         dim3(kBlock), 0, stream, gy.data_ptr<scalar_t>(),
-                         x.data_ptr<scalar_t>(), W1.data_ptr<scalar_t>(),
-                         b1.data_ptr<scalar_t>(), W2.data_ptr<scalar_t>(),
-                         b2.data_ptr<scalar_t>(), gx.data_ptr<scalar_t>(),
-                         gW1.data_ptr<scalar_t>(), gb1.data_ptr<scalar_t>(),
-                         gW2.data_ptr<scalar_t>(), gb2.data_ptr<scalar_t>(),
-                         B, C, W, Tn, S);
-    }
-  });
   DFNO_CHECK_LAUNCH("lift_head");
   return {gx, gW1, gb1, gW2, gb2};
 }

@@ -22,22 +22,15 @@
 
 #include "kernels.h"
 #include "gelu_math.h"
+#include "device_util.h"
 
 namespace {
+
+using namespace dfno_io;
 
 constexpr int kBlock = 256;
 
 typedef float f32x4_mb __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float mb_ld(const float* p) { return *p; }
-__device__ __forceinline__ float mb_ld(const unsigned short* p) {
-  return __uint_as_float(((unsigned int)*p) << 16);
-}
-__device__ __forceinline__ void mb_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void mb_st(unsigned short* p, float v) {
-  __hip_bfloat16 h = __float2bfloat16(v);
-  *p = *reinterpret_cast<unsigned short*>(&h);
-}
 
 // TIO = unsigned short selects bf16 activations (fp32 compute; W and the
 // gW/gb accumulators stay fp32).  PH: phase mask for perf bisection
@@ -84,11 +77,11 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
       float a = 0.f, bb = 0.f;
       if (c < nv) {
         if (row < C) {
-          a = mb_ld(x + ((long)b * C + row) * S + s0 + c);
+          a = ld(x + ((long)b * C + row) * S + s0 + c);
         } else {
           const long off = ((long)b * C + (row - C)) * S + s0 + c;
-          a = mb_ld(gy + off);
-          bb = mb_ld(z + off);
+          a = ld(gy + off);
+          bb = ld(z + off);
         }
       }
       pfa[q] = a;
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
         const float gzv = pfa[q] * dfno_gelu::gelu_grad(pfb[q]);
         gzt[(row - C) * LD + c] = gzv;
         if (WG && c < nv)
-          mb_st(gzout + ((long)b * C + (row - C)) * S + s0 + c, gzv);
+          st(gzout + ((long)b * C + (row - C)) * S + s0 + c, gzv);
       }
     }
     prefetch(t + gridDim.x);
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = mt * 16 + kg * 4 + r;
-          if (i < C) mb_st(gx + ((long)b * C + i) * S + sc, c4[r]);
+          if (i < C) st(gx + ((long)b * C + i) * S + sc, c4[r]);
         }
       }
     }

@@ -11,6 +11,8 @@
 //    - LDS-staged generic fallback for anything else.
 //  * gelu / add+gelu elementwise epilogues (exact erf form, matching
 //    torch.nn.functional.gelu default).
+// One kernel family serves fp32, fp64 and bf16 storage (fp32 arithmetic);
+// the launch tables further down carry the per-dtype tuning.
 //
 // Replaces the reference's einsum + bias-add + separate F.gelu passes
 // (/root/reference/dfno/dfno.py:62-65,291,335-350): 3 activation-sized HBM
@@ -27,82 +29,85 @@
 
 #include "kernels.h"
 #include "gelu_math.h"
+#include "device_util.h"
 
 #define DFNO_CHECK(x, msg) TORCH_CHECK(x, msg)
 
 namespace {
 
+using namespace dfno_io;
+
 constexpr int kBlock = 256;
 
-template <typename T>
-__device__ __forceinline__ T gelu_erf(T z) { return dfno_gelu::gelu(z); }
-
-template <typename T>
-__device__ __forceinline__ T gelu_grad_erf(T z) { return dfno_gelu::gelu_grad(z); }
+// All kernels below are templated on the STORAGE type T (float, double, or
+// bf16 held as unsigned short) and compute in acc_t<T>; elements move only
+// through ld/st and ldv/stv (device_util.h).  VECTOR selects the VEC-wide
+// vector access (the host has checked size and alignment) over per-element
+// access with a ragged tail.
 
 // ---------------------------------------------------------------------------
-// elementwise gelu / add+gelu (vec4, grid-stride)
+// elementwise gelu / add+gelu (VEC per thread, grid-stride)
 // ---------------------------------------------------------------------------
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool VECTOR>
 __global__ void gelu_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long n) {
   long i0 = (long)(blockIdx.x) * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (long i = i0; i * VEC < n; i += stride) {
+  const long nvec = n / VEC;   // whole vectors only when VECTOR
+  for (long i = i0; VECTOR ? i < nvec : i * VEC < n; i += stride) {
     long base = i * VEC;
-    if (base + VEC <= n) {
-      T v[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) v[k] = x[base + k];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) y[base + k] = gelu_erf(v[k]);
+    if (VECTOR || base + VEC <= n) {
+      acc_t<T> v[VEC];
+      ldn<VEC, VECTOR>(x + base, v);
+      stn<VEC, VECTOR>(y + base, [&](int k) { return dfno_gelu::gelu(v[k]); });
     } else {
-      for (long j = base; j < n; ++j) y[j] = gelu_erf(x[j]);
+      for (long j = base; j < n; ++j) st(y + j, dfno_gelu::gelu(ld(x + j)));
     }
   }
 }
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool VECTOR>
 __global__ void gelu_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ z,
                                 T* __restrict__ gz, long n) {
   long i0 = (long)(blockIdx.x) * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (long i = i0; i * VEC < n; i += stride) {
+  const long nvec = n / VEC;   // whole vectors only when VECTOR
+  for (long i = i0; VECTOR ? i < nvec : i * VEC < n; i += stride) {
     long base = i * VEC;
-    if (base + VEC <= n) {
-      T g[VEC], zv[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) { g[k] = gy[base + k]; zv[k] = z[base + k]; }
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) gz[base + k] = g[k] * gelu_grad_erf(zv[k]);
+    if (VECTOR || base + VEC <= n) {
+      acc_t<T> g[VEC], zv[VEC];
+      ldn<VEC, VECTOR>(gy + base, g);
+      ldn<VEC, VECTOR>(z + base, zv);
+      stn<VEC, VECTOR>(gz + base,
+                       [&](int k) { return g[k] * dfno_gelu::gelu_grad(zv[k]); });
     } else {
-      for (long j = base; j < n; ++j) gz[j] = gy[j] * gelu_grad_erf(z[j]);
+      for (long j = base; j < n; ++j)
+        st(gz + j, ld(gy + j) * dfno_gelu::gelu_grad(ld(z + j)));
     }
   }
 }
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool VECTOR>
 __global__ void add_gelu_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                 T* __restrict__ y, T* __restrict__ z, long n) {
   long i0 = (long)(blockIdx.x) * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (long i = i0; i * VEC < n; i += stride) {
+  const long nvec = n / VEC;   // whole vectors only when VECTOR
+  for (long i = i0; VECTOR ? i < nvec : i * VEC < n; i += stride) {
     long base = i * VEC;
-    if (base + VEC <= n) {
-      T av[VEC], bv[VEC];
+    if (VECTOR || base + VEC <= n) {
+      acc_t<T> av[VEC], bv[VEC];
+      ldn<VEC, VECTOR>(a + base, av);
+      ldn<VEC, VECTOR>(b + base, bv);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) { av[k] = a[base + k]; bv[k] = b[base + k]; }
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        T zz = av[k] + bv[k];
-        z[base + k] = zz;
-        y[base + k] = gelu_erf(zz);
-      }
+      for (int k = 0; k < VEC; ++k) av[k] = av[k] + bv[k];
+      stn<VEC, VECTOR>(z + base, [&](int k) { return av[k]; });
+      stn<VEC, VECTOR>(y + base, [&](int k) { return dfno_gelu::gelu(av[k]); });
     } else {
       for (long j = base; j < n; ++j) {
-        T zz = a[j] + b[j];
-        z[j] = zz;
-        y[j] = gelu_erf(zz);
+        acc_t<T> zz = ld(a + j) + ld(b + j);
+        st(z + j, zz);
+        st(y + j, dfno_gelu::gelu(zz));
       }
     }
   }
@@ -110,24 +115,30 @@ __global__ void add_gelu_kernel(const T* __restrict__ a, const T* __restrict__ b
 
 // ---------------------------------------------------------------------------
 // channel mix: x-resident path (I <= IMAX), one thread = VEC consecutive s.
-// W (O x I or transposed) staged in LDS; reads are wave-uniform broadcasts.
+// W (O x I or transposed) and bias staged in LDS in the accumulate type;
+// reads are wave-uniform broadcasts.  Pre-activation order: bias, i
+// ascending, residual; z (when asked for) is that sum, stored before GELU.
 // ---------------------------------------------------------------------------
 
+// IT/OT > 0 pin the channel counts at compile time: the loops fully unroll
+// with folded LDS offsets (see proj_head / dft note: the runtime-bound loop
+// serializes on a per-iteration uniform-load wait)
 template <typename T, int IMAX, int VEC, bool ACT, bool VECTOR,
           int IT = 0, int OT = 0>
 __global__ __launch_bounds__(kBlock) void channel_mix_xres_kernel(
     const T* __restrict__ x, const T* __restrict__ W, const T* __restrict__ bias,
     T* __restrict__ y, T* __restrict__ z,
     int B, int I_, int O_, long S, bool wt, bool has_bias, bool write_z,
-    const T* __restrict__ res = nullptr) {
-  const int I = IT > 0 ? IT : I_;     // see ores note
+    const T* __restrict__ res) {
+  using A = acc_t<T>;
+  const int I = IT > 0 ? IT : I_;
   const int O = OT > 0 ? OT : O_;
   extern __shared__ __align__(16) char smem_raw[];
-  T* Wl = reinterpret_cast<T*>(smem_raw);        // [O*I]
-  T* bl = Wl + (size_t)O * I;                     // [O]
-  for (int k = threadIdx.x; k < O * I; k += blockDim.x) Wl[k] = W[k];
+  A* Wl = reinterpret_cast<A*>(smem_raw);        // [O*I]
+  A* bl = Wl + (size_t)O * I;                     // [O]
+  for (int k = threadIdx.x; k < O * I; k += blockDim.x) Wl[k] = ld(W + k);
   if (has_bias)
-    for (int k = threadIdx.x; k < O; k += blockDim.x) bl[k] = bias[k];
+    for (int k = threadIdx.x; k < O; k += blockDim.x) bl[k] = ld(bias + k);
   __syncthreads();
 
   long nchunks = (S + VEC - 1) / VEC;
@@ -140,68 +151,59 @@ __global__ __launch_bounds__(kBlock) void channel_mix_xres_kernel(
     bool full = (s + VEC) <= S;
     int nv = full ? VEC : (int)(S - s);
 
-    T xr[IMAX][VEC];
+    A xr[IMAX][VEC];
     const T* xb = x + ((long)b * I) * S + s;
-    if constexpr (VECTOR && std::is_same<T, float>::value) {
 #pragma unroll
-      for (int i = 0; i < IMAX; ++i) {
-        if (i < I) {
-        const float4 v = *reinterpret_cast<const float4*>(xb + (long)i * S);
-        xr[i][0] = v.x; xr[i][1] = v.y; xr[i][2] = v.z; xr[i][3] = v.w;
-              }
-      }
-    } else {
+    for (int i = 0; i < IMAX; ++i) {
+      if (i < I) {
+        if constexpr (VECTOR) {
+          ldv<VEC>(xb + (long)i * S, xr[i]);
+        } else {
 #pragma unroll
-      for (int i = 0; i < IMAX; ++i) {
-        if (i < I) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k)
-          xr[i][k] = (full || k < nv) ? xb[(long)i * S + k] : T(0);
-              }
+          for (int k = 0; k < VEC; ++k)
+            xr[i][k] = (full || k < nv) ? ld(xb + (long)i * S + k) : A(0);
+        }
       }
     }
 
-    T* yb = y + ((long)b * O) * S + s;
-    T* zb = write_z ? z + ((long)b * O) * S + s : nullptr;
+    const long off = ((long)b * O) * S + s;
+    T* yb = y + off;
+    T* zb = write_z ? z + off : nullptr;
 #pragma unroll 4
     for (int o = 0; o < (OT > 0 ? OT : 512); ++o) {
       if (OT == 0 && o >= O) break;
-      T acc[VEC];
-      T bv = has_bias ? bl[o] : T(0);
+      A acc[VEC];
+      A bv = has_bias ? bl[o] : A(0);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = bv;
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
-        T wv = wt ? Wl[(size_t)i * O + o] : Wl[(size_t)o * I + i];
+          A wv = wt ? Wl[(size_t)i * O + o] : Wl[(size_t)o * I + i];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] += wv * xr[i][k];
-              }
+          for (int k = 0; k < VEC; ++k) acc[k] += wv * xr[i][k];
+        }
       }
-      if constexpr (VECTOR && std::is_same<T, float>::value) {
+      if constexpr (VECTOR) {
         if (res != nullptr) {
-          const float4 rv = *reinterpret_cast<const float4*>(
-              res + ((long)b * O) * S + (long)o * S + s);
-          acc[0] += rv.x; acc[1] += rv.y; acc[2] += rv.z; acc[3] += rv.w;
+          A rv[VEC];
+          ldv<VEC>(res + off + (long)o * S, rv);
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) acc[k] += rv[k];
         }
-        if (write_z)
-          *reinterpret_cast<float4*>(zb + (long)o * S) =
-              make_float4(acc[0], acc[1], acc[2], acc[3]);
+        if (write_z) stv<VEC>(zb + (long)o * S, acc);
         if (ACT) {
-          *reinterpret_cast<float4*>(yb + (long)o * S) =
-              make_float4(gelu_erf(acc[0]), gelu_erf(acc[1]),
-                          gelu_erf(acc[2]), gelu_erf(acc[3]));
-        } else {
-          *reinterpret_cast<float4*>(yb + (long)o * S) =
-              make_float4(acc[0], acc[1], acc[2], acc[3]);
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) acc[k] = dfno_gelu::gelu(acc[k]);
         }
+        stv<VEC>(yb + (long)o * S, acc);
       } else {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           if (!full && k >= nv) break;
-          if (res != nullptr) acc[k] += res[((long)b * O + o) * S + s + k];
-          if (write_z) zb[(long)o * S + k] = acc[k];
-          yb[(long)o * S + k] = ACT ? gelu_erf(acc[k]) : acc[k];
+          if (res != nullptr) acc[k] += ld(res + off + (long)o * S + k);
+          if (write_z) st(zb + (long)o * S + k, acc[k]);
+          st(yb + (long)o * S + k, ACT ? dfno_gelu::gelu(acc[k]) : acc[k]);
         }
       }
     }
@@ -211,25 +213,28 @@ __global__ __launch_bounds__(kBlock) void channel_mix_xres_kernel(
 // ---------------------------------------------------------------------------
 // channel mix: accumulator-resident path (O <= OMAX; streams over I).
 // Used for the projection head 128 -> 1 and for grad-x of the lift 1 -> C.
+// IU is the unroll of the I stream (part of the per-dtype launch tuning).
+// RES compiles the residual in: unlike in the x-resident kernel, where the
+// test of `res` is free, here even the untaken branch costs the fp32 O <= 8
+// instantiation a VGPR and with it a wave of occupancy.
 // ---------------------------------------------------------------------------
 
 template <typename T, int OMAX, int VEC, bool ACT, bool VECTOR,
-          int IT = 0, int OT = 0>
+          int IT, int OT, int IU, bool RES>
 __global__ __launch_bounds__(kBlock) void channel_mix_ores_kernel(
     const T* __restrict__ x, const T* __restrict__ W, const T* __restrict__ bias,
     T* __restrict__ y, T* __restrict__ z,
-    int B, int I_, int O_, long S, bool wt, bool has_bias, bool write_z) {
-  // IT/OT > 0 pin the channel counts at compile time: the I-stream loop
-  // fully unrolls with folded LDS offsets (see proj_head / dft note: the
-  // runtime-bound loop serializes on a per-iteration uniform-load wait)
+    int B, int I_, int O_, long S, bool wt, bool has_bias, bool write_z,
+    const T* __restrict__ res) {
+  using A = acc_t<T>;
   const int I = IT > 0 ? IT : I_;
   const int O = OT > 0 ? OT : O_;
   extern __shared__ __align__(16) char smem_raw[];
-  T* Wl = reinterpret_cast<T*>(smem_raw);
-  T* bl = Wl + (size_t)O * I;
-  for (int k = threadIdx.x; k < O * I; k += blockDim.x) Wl[k] = W[k];
+  A* Wl = reinterpret_cast<A*>(smem_raw);
+  A* bl = Wl + (size_t)O * I;
+  for (int k = threadIdx.x; k < O * I; k += blockDim.x) Wl[k] = ld(W + k);
   if (has_bias)
-    for (int k = threadIdx.x; k < O; k += blockDim.x) bl[k] = bias[k];
+    for (int k = threadIdx.x; k < O; k += blockDim.x) bl[k] = ld(bias + k);
   __syncthreads();
 
   long nchunks = (S + VEC - 1) / VEC;
@@ -242,65 +247,67 @@ __global__ __launch_bounds__(kBlock) void channel_mix_ores_kernel(
     bool full = (s + VEC) <= S;
     int nv = full ? VEC : (int)(S - s);
 
-    T acc[OMAX][VEC];
+    A acc[OMAX][VEC];
 #pragma unroll
     for (int o = 0; o < OMAX; ++o) {
       if (o < O) {
-      T bv = has_bias ? bl[o] : T(0);
+        A bv = has_bias ? bl[o] : A(0);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) acc[o][k] = bv;
-          }
+        for (int k = 0; k < VEC; ++k) acc[o][k] = bv;
+      }
     }
 
     const T* xb = x + ((long)b * I) * S + s;
-#pragma unroll 8
+#pragma unroll IU
     for (int i = 0; i < (IT > 0 ? IT : 512); ++i) {
       if (IT == 0 && i >= I) break;
-      T xv[VEC];
-      if constexpr (VECTOR && std::is_same<T, float>::value) {
-        const float4 v = *reinterpret_cast<const float4*>(xb + (long)i * S);
-        xv[0] = v.x; xv[1] = v.y; xv[2] = v.z; xv[3] = v.w;
+      A xv[VEC];
+      if constexpr (VECTOR) {
+        ldv<VEC>(xb + (long)i * S, xv);
       } else {
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
-          xv[k] = (full || k < nv) ? xb[(long)i * S + k] : T(0);
+          xv[k] = (full || k < nv) ? ld(xb + (long)i * S + k) : A(0);
       }
 #pragma unroll
       for (int o = 0; o < OMAX; ++o) {
         if (o < O) {
-        T wv = wt ? Wl[(size_t)i * O + o] : Wl[(size_t)o * I + i];
+          A wv = wt ? Wl[(size_t)i * O + o] : Wl[(size_t)o * I + i];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[o][k] += wv * xv[k];
-              }
+          for (int k = 0; k < VEC; ++k) acc[o][k] += wv * xv[k];
+        }
       }
     }
 
-    T* yb = y + ((long)b * O) * S + s;
-    T* zb = write_z ? z + ((long)b * O) * S + s : nullptr;
+    const long off = ((long)b * O) * S + s;
+    T* yb = y + off;
+    T* zb = write_z ? z + off : nullptr;
 #pragma unroll
     for (int o = 0; o < OMAX; ++o) {
       if (o < O) {
-      if constexpr (VECTOR && std::is_same<T, float>::value) {
-        if (write_z)
-          *reinterpret_cast<float4*>(zb + (long)o * S) =
-              make_float4(acc[o][0], acc[o][1], acc[o][2], acc[o][3]);
-        if (ACT) {
-          *reinterpret_cast<float4*>(yb + (long)o * S) =
-              make_float4(gelu_erf(acc[o][0]), gelu_erf(acc[o][1]),
-                          gelu_erf(acc[o][2]), gelu_erf(acc[o][3]));
-        } else {
-          *reinterpret_cast<float4*>(yb + (long)o * S) =
-              make_float4(acc[o][0], acc[o][1], acc[o][2], acc[o][3]);
-        }
-      } else {
+        if constexpr (VECTOR) {
+          if constexpr (RES) {
+            A rv[VEC];
+            ldv<VEC>(res + off + (long)o * S, rv);
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          if (!full && k >= nv) break;
-          if (write_z) zb[(long)o * S + k] = acc[o][k];
-          yb[(long)o * S + k] = ACT ? gelu_erf(acc[o][k]) : acc[o][k];
+            for (int k = 0; k < VEC; ++k) acc[o][k] += rv[k];
+          }
+          if (write_z) stv<VEC>(zb + (long)o * S, acc[o]);
+          if (ACT) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) acc[o][k] = dfno_gelu::gelu(acc[o][k]);
+          }
+          stv<VEC>(yb + (long)o * S, acc[o]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            if (!full && k >= nv) break;
+            if constexpr (RES) acc[o][k] += ld(res + off + (long)o * S + k);
+            if (write_z) st(zb + (long)o * S + k, acc[o][k]);
+            st(yb + (long)o * S + k, ACT ? dfno_gelu::gelu(acc[o][k]) : acc[o][k]);
+          }
         }
       }
-          }
     }
   }
 }
@@ -349,134 +356,164 @@ __global__ __launch_bounds__(kBlock) void channel_mix_lds_kernel(
           acc += wv * xt[i * TS + s];
         }
         if (write_z) zb[(long)o * S] = acc;
-        yb[(long)o * S] = ACT ? gelu_erf(acc) : acc;
+        yb[(long)o * S] = ACT ? dfno_gelu::gelu(acc) : acc;
       }
     }
   }
 }
 
-int grid_for(long work, int block) {
-  long g = (work + block - 1) / block;
-  long cap = 256L * 8;  // 256 CUs, a few blocks each; grid-stride the rest
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+// ---------------------------------------------------------------------------
+// launch tables: the per-dtype tuning (caps, vector width, compile-time
+// pins, grid cap), one table for fp32/fp64 and one for bf16
+// ---------------------------------------------------------------------------
 
+// 256 CUs, a few blocks each; grid-stride the rest
+constexpr long kGridCap = 256L * 8;
+constexpr long kGridCapBf16 = 256L * 16;
+
+// what every channel-mix kernel takes, plus the launch geometry
 template <typename T>
-bool can_vectorize(const T* x, const T* y, const T* z, long S, bool write_z) {
-  if (!std::is_same<T, float>::value) return false;
+struct MixLaunch {
+  const T* x; const T* W; const T* bias; T* y; T* z;
+  int B, I, O; long S;
+  bool wt, has_bias, act, write_z;
+  const T* res;
+  int grid; hipStream_t stream;
+};
+
+// KERNEL<T, CAP, VEC, act, VECTOR, pins...>; W and bias sit in LDS
+#define CMIX(KERNEL, CAP, VEC, V, ...)                                          \
+  do {                                                                          \
+    const size_t smem = sizeof(acc_t<T>) * ((size_t)a.O * a.I + a.O);           \
+    if (a.act) {                                                                \
+      hipLaunchKernelGGL((KERNEL<T, CAP, VEC, true, V, __VA_ARGS__>),           \
+                         dim3(a.grid), dim3(kBlock), smem, a.stream, a.x, a.W,  \
+                         a.bias, a.y, a.z, a.B, a.I, a.O, a.S, a.wt,            \
+                         a.has_bias, a.write_z, a.res);                         \
+    } else {                                                                    \
+      hipLaunchKernelGGL((KERNEL<T, CAP, VEC, false, V, __VA_ARGS__>),          \
+                         dim3(a.grid), dim3(kBlock), smem, a.stream, a.x, a.W,  \
+                         a.bias, a.y, a.z, a.B, a.I, a.O, a.S, a.wt,            \
+                         a.has_bias, a.write_z, a.res);                         \
+    }                                                                           \
+  } while (0)
+
+bool can_vectorize(const float* x, const float* y, const float* z, long S,
+                   bool write_z) {
   if (S % 4 != 0) return false;
   auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   return aligned(x) && aligned(y) && (!write_z || aligned(z));
 }
+bool can_vectorize(const double*, const double*, const double*, long, bool) {
+  return false;
+}
 
+// LDS-staged generic path (fp32/fp64 only); pick the largest tile that keeps
+// the x tile within 64 KiB (>= 2 blocks/CU of LDS headroom)
+template <typename T>
+void launch_channel_mix_lds(const MixLaunch<T>& a) {
+  const int grid = launch_grid((long)a.B * ((a.S + kBlock - 1) / kBlock) * kBlock,
+                               kBlock, kGridCap);
+#define CMIX_LDS(TS)                                                            \
+  {                                                                             \
+    size_t smem_lds = sizeof(T) * ((size_t)a.I * TS + (size_t)a.O * a.I + a.O); \
+    if (a.act) {                                                                \
+      hipLaunchKernelGGL((channel_mix_lds_kernel<T, true, TS>), dim3(grid),     \
+                         dim3(kBlock), smem_lds, a.stream, a.x, a.W, a.bias,    \
+                         a.y, a.z, a.B, a.I, a.O, a.S, a.wt, a.has_bias,        \
+                         a.write_z);                                            \
+    } else {                                                                    \
+      hipLaunchKernelGGL((channel_mix_lds_kernel<T, false, TS>), dim3(grid),    \
+                         dim3(kBlock), smem_lds, a.stream, a.x, a.W, a.bias,    \
+                         a.y, a.z, a.B, a.I, a.O, a.S, a.wt, a.has_bias,        \
+                         a.write_z);                                            \
+    }                                                                           \
+  }
+  size_t per_s = sizeof(T) * (size_t)a.I;
+  size_t wbytes = sizeof(T) * ((size_t)a.O * a.I + a.O);
+  if (per_s * 256 + wbytes <= 64 * 1024) { CMIX_LDS(256) }
+  else if (per_s * 128 + wbytes <= 96 * 1024) { CMIX_LDS(128) }
+  else if (per_s * 64 + wbytes <= 128 * 1024) { CMIX_LDS(64) }
+  else {
+    TORCH_CHECK(per_s * 32 + wbytes <= 160 * 1024,
+                "channel_mix: I/O too large for LDS tile");
+    CMIX_LDS(32)
+  }
+#undef CMIX_LDS
+}
+
+// fp32 / fp64: VEC 4, float4 access when size and alignment allow
 template <typename T>
 void launch_channel_mix(const T* x, const T* W, const T* bias, T* y, T* z,
                         int B, int I, int O, long S, bool wt, bool has_bias,
                         bool act, bool write_z, hipStream_t stream,
                         const T* res = nullptr) {
-  // effective input count for residency decisions
-  long nchunk_work = (long)B * ((S + 3) / 4);
-  int grid = grid_for(nchunk_work, kBlock);
-  size_t smem = sizeof(T) * ((size_t)O * I + O);
+  constexpr bool kFloat = std::is_same<T, float>::value;
+  const MixLaunch<T> a{x, W, bias, y, z, B, I, O, S, wt, has_bias, act, write_z,
+                       res, launch_grid((long)B * ((S + 3) / 4), kBlock, kGridCap),
+                       stream};
   const bool vec = can_vectorize(x, y, z, S, write_z);
-
-  // fold the flagship channel counts at compile time (see kernel note)
-  const bool f2020 = (I == 20 && O == 20);
-  const bool f12820 = (I == 128 && O == 20);
-#define CMIX_LAUNCH(KERNEL, CAP, A, V)                                          \
-  if (f2020) {                                                                  \
-    hipLaunchKernelGGL((KERNEL<T, CAP, 4, A, V, 20, 20>), dim3(grid),           \
-                       dim3(kBlock), smem, stream, x, W, bias, y, z, B, I, O,   \
-                       S, wt, has_bias, write_z);                               \
-  } else if (f12820) {                                                          \
-    hipLaunchKernelGGL((KERNEL<T, CAP, 4, A, V, 128, 20>), dim3(grid),          \
-                       dim3(kBlock), smem, stream, x, W, bias, y, z, B, I, O,   \
-                       S, wt, has_bias, write_z);                               \
-  } else {                                                                      \
-    hipLaunchKernelGGL((KERNEL<T, CAP, 4, A, V>), dim3(grid), dim3(kBlock),     \
-                       smem, stream, x, W, bias, y, z, B, I, O, S, wt,          \
-                       has_bias, write_z);                                      \
-  }
-#define CMIX_LAUNCH_RES(KERNEL, CAP, A, V)                                      \
-  if (f2020) {                                                                  \
-    hipLaunchKernelGGL((KERNEL<T, CAP, 4, A, V, 20, 20>), dim3(grid),           \
-                       dim3(kBlock), smem, stream, x, W, bias, y, z, B, I, O,   \
-                       S, wt, has_bias, write_z, res);                          \
-  } else {                                                                      \
-    hipLaunchKernelGGL((KERNEL<T, CAP, 4, A, V>), dim3(grid), dim3(kBlock),     \
-                       smem, stream, x, W, bias, y, z, B, I, O, S, wt,          \
-                       has_bias, write_z, res);                                 \
-  }
-#define CMIX_DISPATCH(KERNEL, CAP)                                              \
-  if (act) {                                                                    \
-    if (vec) { CMIX_LAUNCH(KERNEL, CAP, true, true) }                           \
-    else { CMIX_LAUNCH(KERNEL, CAP, true, false) }                              \
-  } else {                                                                      \
-    if (vec) { CMIX_LAUNCH(KERNEL, CAP, false, true) }                          \
-    else { CMIX_LAUNCH(KERNEL, CAP, false, false) }                             \
-  }
-
-#define CMIX_DISPATCH_RES(KERNEL, CAP)                                          \
-  if (act) {                                                                    \
-    if (vec) { CMIX_LAUNCH_RES(KERNEL, CAP, true, true) }                       \
-    else { CMIX_LAUNCH_RES(KERNEL, CAP, true, false) }                          \
-  } else {                                                                      \
-    if (vec) { CMIX_LAUNCH_RES(KERNEL, CAP, false, true) }                      \
-    else { CMIX_LAUNCH_RES(KERNEL, CAP, false, false) }                         \
-  }
-  if (res != nullptr) {
-    TORCH_CHECK(I <= 32, "channel_mix with residual needs I <= 32");
-    if (I <= 8) { CMIX_DISPATCH_RES(channel_mix_xres_kernel, 8) }
-    else if (I <= 16) { CMIX_DISPATCH_RES(channel_mix_xres_kernel, 16) }
-    else if (I <= 24) { CMIX_DISPATCH_RES(channel_mix_xres_kernel, 24) }
-    else { CMIX_DISPATCH_RES(channel_mix_xres_kernel, 32) }
-    return;
-  }
-  if (I <= 8) { CMIX_DISPATCH(channel_mix_xres_kernel, 8) }
-  else if (I <= 16) { CMIX_DISPATCH(channel_mix_xres_kernel, 16) }
-  else if (I <= 24) { CMIX_DISPATCH(channel_mix_xres_kernel, 24) }
-  else if (I <= 32) { CMIX_DISPATCH(channel_mix_xres_kernel, 32) }
-  else if (O <= 4) { CMIX_DISPATCH(channel_mix_ores_kernel, 4) }
-  else if (O <= 8) { CMIX_DISPATCH(channel_mix_ores_kernel, 8) }
-  else if (O <= 16) { CMIX_DISPATCH(channel_mix_ores_kernel, 16) }
-  else if (O <= 24 && std::is_same<T, float>::value) { CMIX_DISPATCH(channel_mix_ores_kernel, 24) }
-  else if (O <= 32 && std::is_same<T, float>::value) { CMIX_DISPATCH(channel_mix_ores_kernel, 32) }
-  else {
-    // LDS-staged generic path; pick the largest tile that keeps the x tile
-    // within 64 KiB (>= 2 blocks/CU of LDS headroom)
-    int grid2 = grid_for((long)B * ((S + kBlock - 1) / kBlock) * kBlock, kBlock);
-#define CMIX_LDS(TS)                                                            \
-  {                                                                             \
-    size_t smem_lds = sizeof(T) * ((size_t)I * TS + (size_t)O * I + O);         \
-    if (act) {                                                                  \
-      hipLaunchKernelGGL((channel_mix_lds_kernel<T, true, TS>), dim3(grid2),    \
-                         dim3(kBlock), smem_lds, stream, x, W, bias, y, z, B,   \
-                         I, O, S, wt, has_bias, write_z);                       \
+#define CMIX_V(KERNEL, CAP, ...)                                                \
+  do {                                                                          \
+    if constexpr (kFloat) {                                                     \
+      if (vec) CMIX(KERNEL, CAP, 4, true, __VA_ARGS__);                         \
+      else CMIX(KERNEL, CAP, 4, false, __VA_ARGS__);                            \
     } else {                                                                    \
-      hipLaunchKernelGGL((channel_mix_lds_kernel<T, false, TS>), dim3(grid2),   \
-                         dim3(kBlock), smem_lds, stream, x, W, bias, y, z, B,   \
-                         I, O, S, wt, has_bias, write_z);                       \
+      CMIX(KERNEL, CAP, 4, false, __VA_ARGS__);                                 \
     }                                                                           \
-  }
-    size_t per_s = sizeof(T) * (size_t)I;
-    size_t wbytes = sizeof(T) * ((size_t)O * I + O);
-    if (per_s * 256 + wbytes <= 64 * 1024) { CMIX_LDS(256) }
-    else if (per_s * 128 + wbytes <= 96 * 1024) { CMIX_LDS(128) }
-    else if (per_s * 64 + wbytes <= 128 * 1024) { CMIX_LDS(64) }
-    else {
-      TORCH_CHECK(per_s * 32 + wbytes <= 160 * 1024,
-                  "channel_mix: I/O too large for LDS tile");
-      CMIX_LDS(32)
+  } while (0)
+  TORCH_CHECK(res == nullptr || I <= 32, "channel_mix with residual needs I <= 32");
+  // the flagship channel counts fold at compile time (see kernel note)
+  if (I == 20 && O == 20) CMIX_V(channel_mix_xres_kernel, 24, 20, 20);
+  else if (I <= 8) CMIX_V(channel_mix_xres_kernel, 8, 0, 0);
+  else if (I <= 16) CMIX_V(channel_mix_xres_kernel, 16, 0, 0);
+  else if (I <= 24) CMIX_V(channel_mix_xres_kernel, 24, 0, 0);
+  else if (I <= 32) CMIX_V(channel_mix_xres_kernel, 32, 0, 0);
+  else if (O <= 4) CMIX_V(channel_mix_ores_kernel, 4, 0, 0, 8, false);
+  else if (O <= 8) CMIX_V(channel_mix_ores_kernel, 8, 0, 0, 8, false);
+  else if (O <= 16) CMIX_V(channel_mix_ores_kernel, 16, 0, 0, 8, false);
+  else if (kFloat && O <= 32) {
+    if constexpr (kFloat) {   // float only: the wide caps are not built for double
+      if (I == 128 && O == 20) CMIX_V(channel_mix_ores_kernel, 24, 128, 20, 8, false);
+      else if (O <= 24) CMIX_V(channel_mix_ores_kernel, 24, 0, 0, 8, false);
+      else CMIX_V(channel_mix_ores_kernel, 32, 0, 0, 8, false);
     }
-#undef CMIX_LDS
+  } else {
+    launch_channel_mix_lds(a);
   }
-#undef CMIX_DISPATCH_RES
-#undef CMIX_DISPATCH
-#undef CMIX_LAUNCH_RES
-#undef CMIX_LAUNCH
+#undef CMIX_V
 }
+
+// bf16: always vector access (S % 8 == 0 is required); VEC 8 at the narrow
+// caps, VEC 4 at the wide ones (xr[24][8] / acc[24][8] = 192 VGPRs would
+// spill).  Shapes outside the table raise.
+void launch_channel_mix_bf16(const MixLaunch<unsigned short>& a) {
+  using T = unsigned short;
+  const int I = a.I, O = a.O;
+  // the accumulator-resident kernel compiles its residual in or out
+#define CMIX_ORES(CAP, VEC, IT, OT)                                             \
+  do {                                                                          \
+    if (a.res != nullptr)                                                       \
+      CMIX(channel_mix_ores_kernel, CAP, VEC, true, IT, OT, 4, true);           \
+    else                                                                        \
+      CMIX(channel_mix_ores_kernel, CAP, VEC, true, IT, OT, 4, false);          \
+  } while (0)
+  // compile-time-pinned hot shapes first (block mixes, projection lift and
+  // its transpose, channel lift, projection head)
+  if (I == 20 && O == 20) CMIX(channel_mix_xres_kernel, 24, 4, true, 20, 20);
+  else if (I == 20 && O == 128) CMIX(channel_mix_xres_kernel, 24, 4, true, 20, 128);
+  else if (I == 2 && O == 20) CMIX(channel_mix_xres_kernel, 8, 8, true, 2, 20);
+  else if (I == 128 && O == 20) CMIX_ORES(24, 4, 128, 20);
+  else if (I == 128 && O == 1) CMIX_ORES(8, 8, 128, 1);
+  else if (I <= 8) CMIX(channel_mix_xres_kernel, 8, 8, true, 0, 0);
+  else if (I <= 24) CMIX(channel_mix_xres_kernel, 24, 4, true, 0, 0);
+  else if (I <= 32) CMIX(channel_mix_xres_kernel, 32, 4, true, 0, 0);
+  else if (O <= 8) CMIX_ORES(8, 8, 0, 0);
+  else if (O <= 24) CMIX_ORES(24, 4, 0, 0);
+  else TORCH_CHECK(false, "bf16 channel mix: unsupported shape I=", I, " O=", O);
+#undef CMIX_ORES
+}
+#undef CMIX
 
 }  // namespace
 
@@ -484,16 +521,9 @@ void launch_channel_mix(const T* x, const T* W, const T* bias, T* y, T* z,
 // host entry points
 // ---------------------------------------------------------------------------
 
-static void check_f(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kDouble,
-              name, " must be float32/float64");
-}
-
 std::vector<at::Tensor> channel_mix_fwd(const at::Tensor& x, const at::Tensor& W,
                                         const at::Tensor& b, bool act) {
-  check_f(x, "x"); check_f(W, "W");
+  check_real(x, "x"); check_real(W, "W");
   TORCH_CHECK(x.dim() == 3, "x must be [B,I,S]");
   int B = (int)x.size(0), I = (int)x.size(1);
   long S = x.size(2);
@@ -518,7 +548,7 @@ std::vector<at::Tensor> channel_mix_fwd(const at::Tensor& x, const at::Tensor& W
 }
 
 at::Tensor channel_mix_fwd_t(const at::Tensor& gz, const at::Tensor& W) {
-  check_f(gz, "gz"); check_f(W, "W");
+  check_real(gz, "gz"); check_real(W, "W");
   TORCH_CHECK(gz.dim() == 3, "gz must be [B,O,S]");
   int B = (int)gz.size(0), O = (int)gz.size(1);
   long S = gz.size(2);
@@ -542,7 +572,7 @@ at::Tensor channel_mix_fwd_t(const at::Tensor& gz, const at::Tensor& W) {
 
 std::vector<at::Tensor> linear_res_gelu_fwd(const at::Tensor& x, const at::Tensor& W,
                                             const at::Tensor& res) {
-  check_f(x, "x"); check_f(W, "W"); check_f(res, "res");
+  check_real(x, "x"); check_real(W, "W"); check_real(res, "res");
   TORCH_CHECK(x.dim() == 3 && res.dim() == 3, "x/res must be [B,*,S]");
   int B = (int)x.size(0), I = (int)x.size(1);
   long S = x.size(2);
@@ -566,29 +596,29 @@ std::vector<at::Tensor> linear_res_gelu_fwd(const at::Tensor& x, const at::Tenso
 }
 
 at::Tensor gelu_fwd(const at::Tensor& x) {
-  check_f(x, "x");
+  check_real(x, "x");
   auto y = at::empty_like(x);
   long n = x.numel();
   if (n == 0) return y;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "gelu_fwd", [&] {
-    int grid = grid_for((n + 3) / 4, kBlock);
-    hipLaunchKernelGGL((gelu_fwd_kernel<scalar_t, 4>), dim3(grid), dim3(kBlock), 0,
+    int grid = launch_grid((n + 3) / 4, kBlock, kGridCap);
+    hipLaunchKernelGGL((gelu_fwd_kernel<scalar_t, 4, false>), dim3(grid), dim3(kBlock), 0,
                        stream, x.data_ptr<scalar_t>(), y.data_ptr<scalar_t>(), n);
   });
   return y;
 }
 
 at::Tensor gelu_bwd(const at::Tensor& gy, const at::Tensor& z) {
-  check_f(gy, "gy"); check_f(z, "z");
+  check_real(gy, "gy"); check_real(z, "z");
   TORCH_CHECK(gy.numel() == z.numel(), "gelu_bwd size mismatch");
   auto gz = at::empty_like(gy);
   long n = gy.numel();
   if (n == 0) return gz;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   AT_DISPATCH_FLOATING_TYPES(gy.scalar_type(), "gelu_bwd", [&] {
-    int grid = grid_for((n + 3) / 4, kBlock);
-    hipLaunchKernelGGL((gelu_bwd_kernel<scalar_t, 4>), dim3(grid), dim3(kBlock), 0,
+    int grid = launch_grid((n + 3) / 4, kBlock, kGridCap);
+    hipLaunchKernelGGL((gelu_bwd_kernel<scalar_t, 4, false>), dim3(grid), dim3(kBlock), 0,
                        stream, gy.data_ptr<scalar_t>(), z.data_ptr<scalar_t>(),
                        gz.data_ptr<scalar_t>(), n);
   });
@@ -596,7 +626,7 @@ at::Tensor gelu_bwd(const at::Tensor& gy, const at::Tensor& z) {
 }
 
 std::vector<at::Tensor> add_gelu_fwd(const at::Tensor& a, const at::Tensor& b) {
-  check_f(a, "a"); check_f(b, "b");
+  check_real(a, "a"); check_real(b, "b");
   TORCH_CHECK(a.sizes() == b.sizes(), "add_gelu shape mismatch");
   auto y = at::empty_like(a);
   auto z = at::empty_like(a);
@@ -604,11 +634,89 @@ std::vector<at::Tensor> add_gelu_fwd(const at::Tensor& a, const at::Tensor& b) {
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   if (n == 0) return {y, z};
   AT_DISPATCH_FLOATING_TYPES(a.scalar_type(), "add_gelu_fwd", [&] {
-    int grid = grid_for((n + 3) / 4, kBlock);
-    hipLaunchKernelGGL((add_gelu_kernel<scalar_t, 4>), dim3(grid), dim3(kBlock), 0,
+    int grid = launch_grid((n + 3) / 4, kBlock, kGridCap);
+    hipLaunchKernelGGL((add_gelu_kernel<scalar_t, 4, false>), dim3(grid), dim3(kBlock), 0,
                        stream, a.data_ptr<scalar_t>(), b.data_ptr<scalar_t>(),
                        y.data_ptr<scalar_t>(), z.data_ptr<scalar_t>(), n);
   });
+  return {y, z};
+}
+
+// ---------------------------------------------------------------------------
+// bf16-storage entry points (the bf16 compute config).  Storage is bf16
+// (halves every activation's HBM traffic; these ops are bandwidth-bound),
+// arithmetic is fp32.  Vector IO is 8 bf16 per lane (16 B, the coalescing
+// sweet spot), so sizes must be multiples of 8.
+// ---------------------------------------------------------------------------
+
+std::vector<at::Tensor> bf16_channel_mix(const at::Tensor& x, const at::Tensor& W,
+                                         const at::Tensor& b, bool act, bool wt,
+                                         bool write_z, const at::Tensor& res) {
+  check_bf16(x, "x"); check_bf16(W, "W");
+  const int B = (int)x.size(0);
+  const int I = (int)x.size(1);
+  const long S = x.size(2);
+  const int O = wt ? (int)W.size(1) : (int)W.size(0);
+  TORCH_CHECK(S % 8 == 0, "bf16 channel mix: S must be a multiple of 8");
+  const bool has_bias = b.defined() && b.numel() > 0;
+  if (has_bias) check_bf16(b, "b");
+  const bool has_res = res.defined() && res.numel() > 0;
+  if (has_res) check_bf16(res, "res");
+
+  auto y = at::empty({B, O, S}, x.options());
+  auto z = write_z ? at::empty({B, O, S}, x.options()) : at::empty({0}, x.options());
+  if (x.numel() == 0) return {y, z};
+
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_channel_mix_bf16(
+      {usp(x), usp(W), has_bias ? usp(b) : nullptr, usp_mut(y),
+       write_z ? usp_mut(z) : nullptr, B, I, O, S, wt, has_bias, act, write_z,
+       has_res ? usp(res) : nullptr,
+       launch_grid((long)B * (S / 8), kBlock, kGridCapBf16), stream});
+  DFNO_CHECK_LAUNCH("bf16_channel_mix");
+  return {y, z};
+}
+
+at::Tensor bf16_gelu_fwd(const at::Tensor& x) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.numel() % 8 == 0, "bf16 gelu: numel must be a multiple of 8");
+  auto y = at::empty_like(x);
+  if (x.numel() == 0) return y;
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const long n = x.numel();
+  hipLaunchKernelGGL((gelu_fwd_kernel<unsigned short, 8, true>),
+                     dim3(launch_grid(n / 8, kBlock, kGridCapBf16)), dim3(kBlock),
+                     0, stream, usp(x), usp_mut(y), n);
+  DFNO_CHECK_LAUNCH("bf16_gelu");
+  return y;
+}
+
+at::Tensor bf16_gelu_bwd(const at::Tensor& gy, const at::Tensor& z) {
+  check_bf16(gy, "gy"); check_bf16(z, "z");
+  TORCH_CHECK(gy.numel() % 8 == 0, "bf16 gelu bwd: numel % 8");
+  auto gz = at::empty_like(gy);
+  if (gy.numel() == 0) return gz;
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const long n = gy.numel();
+  hipLaunchKernelGGL((gelu_bwd_kernel<unsigned short, 8, true>),
+                     dim3(launch_grid(n / 8, kBlock, kGridCapBf16)), dim3(kBlock),
+                     0, stream, usp(gy), usp(z), usp_mut(gz), n);
+  DFNO_CHECK_LAUNCH("bf16_gelu_bwd");
+  return gz;
+}
+
+std::vector<at::Tensor> bf16_add_gelu(const at::Tensor& a, const at::Tensor& b) {
+  check_bf16(a, "a"); check_bf16(b, "b");
+  TORCH_CHECK(a.numel() == b.numel() && a.numel() % 8 == 0, "bf16 add_gelu shape");
+  auto y = at::empty_like(a);
+  auto z = at::empty_like(a);
+  if (a.numel() == 0) return {y, z};
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const long n = a.numel();
+  hipLaunchKernelGGL((add_gelu_kernel<unsigned short, 8, true>),
+                     dim3(launch_grid(n / 8, kBlock, kGridCapBf16)), dim3(kBlock),
+                     0, stream, usp(a), usp(b), usp_mut(y), usp_mut(z), n);
+  DFNO_CHECK_LAUNCH("bf16_add_gelu");
   return {y, z};
 }
 
@@ -625,13 +733,6 @@ std::vector<at::Tensor> add_gelu_fwd(const at::Tensor& a, const at::Tensor& b) {
 // ---------------------------------------------------------------------------
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ T gw_wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <typename T, int ICAP, int OW, bool BIAS, bool VECTOR>
 __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
@@ -726,12 +827,12 @@ __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
 #pragma unroll
       for (int i = 0; i < ICAP; ++i) {
         if (i < I) {
-          T v = gw_wave_sum(acc[w][i]);
+          T v = wave_sum(acc[w][i]);
           if (lane == 0 && v != T(0)) atomicAdd(&gW[(size_t)(o0 + w) * I + i], v);
         }
       }
       if (BIAS) {
-        T v = gw_wave_sum(bacc[w]);
+        T v = wave_sum(bacc[w]);
         if (lane == 0 && v != T(0)) atomicAdd(&gb[o0 + w], v);
       }
     }
@@ -934,13 +1035,13 @@ __global__ __launch_bounds__(kBlock) void gw_outer_glds3_kernel(
 #pragma unroll
       for (int i = 0; i < ICAP; ++i) {
         if (i < I) {
-          float v = gw_wave_sum(acc[w][i]);
+          float v = wave_sum(acc[w][i]);
           if (lane == 0 && v != 0.f)
             atomicAdd(reinterpret_cast<float*>(&gW[(size_t)(o0 + w) * I + i]), v);
         }
       }
       if (want_bias) {
-        float v = gw_wave_sum(bacc[w]);
+        float v = wave_sum(bacc[w]);
         if (lane == 0 && v != 0.f)
           atomicAdd(reinterpret_cast<float*>(&gb[o0 + w]), v);
       }
@@ -1046,7 +1147,7 @@ __global__ __launch_bounds__(kBlock) void gw_mfma_f32_kernel(
 
 std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor& x,
                                           bool want_bias) {
-  check_f(gz, "gz"); check_f(x, "x");
+  check_real(gz, "gz"); check_real(x, "x");
   TORCH_CHECK(gz.dim() == 3 && x.dim() == 3, "gz/x must be [B,*,S]");
   int B = (int)gz.size(0), O = (int)gz.size(1), I = (int)x.size(1);
   long S = gz.size(2);
@@ -1295,28 +1396,6 @@ struct AdamTabB {
   int nt;
 };
 
-__device__ __forceinline__ void adam_load8b(const unsigned short* p, float* o) {
-  const uint4 raw = *reinterpret_cast<const uint4*>(p);
-  const unsigned int w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    o[2 * k] = __uint_as_float((w[k] & 0xffffu) << 16);
-    o[2 * k + 1] = __uint_as_float((w[k] >> 16) << 16);
-  }
-}
-
-__device__ __forceinline__ void adam_store8b(unsigned short* p, const float* v) {
-  uint4 raw;
-  unsigned int w[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    __hip_bfloat162 h2 = __float22bfloat162_rn(float2{v[2 * k], v[2 * k + 1]});
-    w[k] = *reinterpret_cast<unsigned int*>(&h2);
-  }
-  raw.x = w[0]; raw.y = w[1]; raw.z = w[2]; raw.w = w[3];
-  *reinterpret_cast<uint4*>(p) = raw;
-}
-
 __global__ __launch_bounds__(kBlock) void adam_multi_bf16_kernel(
     AdamTabB tab, long total8, float lr, float b1, float b2, float eps,
     float wd) {
@@ -1330,10 +1409,10 @@ __global__ __launch_bounds__(kBlock) void adam_multi_bf16_kernel(
     const float c1 = tab.c1[t], c2 = tab.c2[t];
     if (j + 8 <= tab.nn[t]) {
       float pr[8], gr[8], mr[8], vr[8];
-      adam_load8b(tab.p[t] + j, pr);
-      adam_load8b(tab.g[t] + j, gr);
-      adam_load8b(tab.m[t] + j, mr);
-      adam_load8b(tab.v[t] + j, vr);
+      load8(tab.p[t] + j, pr);
+      load8(tab.g[t] + j, gr);
+      load8(tab.m[t] + j, mr);
+      load8(tab.v[t] + j, vr);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float gg = gr[k] + wd * pr[k];
@@ -1341,9 +1420,9 @@ __global__ __launch_bounds__(kBlock) void adam_multi_bf16_kernel(
         vr[k] = b2 * vr[k] + (1.f - b2) * gg * gg;
         pr[k] -= lr * (mr[k] / c1) / (sqrtf(vr[k] / c2) + eps);
       }
-      adam_store8b(tab.p[t] + j, pr);
-      adam_store8b(tab.m[t] + j, mr);
-      adam_store8b(tab.v[t] + j, vr);
+      store8(tab.p[t] + j, pr);
+      store8(tab.m[t] + j, mr);
+      store8(tab.v[t] + j, vr);
     } else {
       for (long e = j; e < tab.nn[t]; ++e) {   // ragged tail, scalar
         float pv = __uint_as_float(((unsigned int)tab.p[t][e]) << 16);
@@ -1454,7 +1533,7 @@ static std::vector<int64_t> adam_step_batch_impl(
   long btotal8 = 0;
   auto flush_bf16 = [&]() {
     if (btab.nt == 0) return;
-    int grid = grid_for(btotal8, kBlock);
+    int grid = launch_grid(btotal8, kBlock, kGridCap);
     hipLaunchKernelGGL(adam_multi_bf16_kernel, dim3(grid), dim3(kBlock), 0,
                        stream, btab, btotal8, (float)lr, (float)beta1,
                        (float)beta2, (float)eps, (float)weight_decay);
@@ -1506,7 +1585,7 @@ static std::vector<int64_t> adam_step_batch_impl(
   long total4 = 0;
   auto flush_ragged = [&]() {
     if (rag.nt == 0) return;
-    int grid = grid_for(total4, kBlock);
+    int grid = launch_grid(total4, kBlock, kGridCap);
     hipLaunchKernelGGL(adam_multi_kernel, dim3(grid), dim3(kBlock), 0, stream,
                        rag, total4, (float)lr, (float)beta1, (float)beta2,
                        (float)eps, (float)weight_decay);
@@ -1592,7 +1671,7 @@ std::vector<int64_t> adam_step_batch_fp8_(
 void adam_step_(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Tensor& v,
                 double lr, double beta1, double beta2, double eps,
                 double weight_decay, int64_t step) {
-  check_f(p, "p"); check_f(g, "g"); check_f(m, "m"); check_f(v, "v");
+  check_real(p, "p"); check_real(g, "g"); check_real(m, "m"); check_real(v, "v");
   long n = p.numel();
   TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "adam: size mismatch");
   if (n == 0) return;
@@ -1605,7 +1684,7 @@ void adam_step_(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Tensor& v
                ((reinterpret_cast<uintptr_t>(g.data_ptr()) & 15) == 0) &&
                ((reinterpret_cast<uintptr_t>(m.data_ptr()) & 15) == 0) &&
                ((reinterpret_cast<uintptr_t>(v.data_ptr()) & 15) == 0);
-    int grid = grid_for(vec ? (n + 3) / 4 : n, kBlock);
+    int grid = launch_grid(vec ? (n + 3) / 4 : n, kBlock, kGridCap);
     if (vec) {
       hipLaunchKernelGGL((adam_step_kernel<scalar_t, true>), dim3(grid), dim3(kBlock),
                          0, stream, p.data_ptr<scalar_t>(), g.data_ptr<scalar_t>(),

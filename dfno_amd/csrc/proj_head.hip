@@ -27,38 +27,15 @@
 
 #include "kernels.h"
 #include "gelu_math.h"
+#include "device_util.h"
 
 namespace {
+
+using namespace dfno_io;
 
 constexpr int kBlock = 256;
 
 typedef float f32x4_ph __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ T gelu_erf_(T z) { return dfno_gelu::gelu(z); }
-
-__device__ __forceinline__ float ph_ld(const float* p) { return *p; }
-__device__ __forceinline__ double ph_ld(const double* p) { return *p; }
-__device__ __forceinline__ float ph_ld(const unsigned short* p) {
-  return __uint_as_float(((unsigned int)*p) << 16);
-}
-__device__ __forceinline__ void ph_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void ph_st(double* p, double v) { *p = v; }
-__device__ __forceinline__ void ph_st(unsigned short* p, float v) {
-  __hip_bfloat16 h = __float2bfloat16(v);
-  *p = *reinterpret_cast<unsigned short*>(&h);
-}
-
-template <typename T>
-__device__ __forceinline__ T gelu_grad_erf_(T z) { return dfno_gelu::gelu_grad(z); }
-
-// butterfly sum over the 64-lane wave
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 template <typename T, int IMAX, int O2MAX, int VEC, bool VECTOR,
           int MT = 0, int IT = 0, typename TIO = T>
@@ -104,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
         if (i < I) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
-          xr[i][k] = (full || k < nv) ? (T)ph_ld(xb + (long)i * S + k) : T(0);
+          xr[i][k] = (full || k < nv) ? (T)ld(xb + (long)i * S + k) : T(0);
               }
       }
     }
@@ -134,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
               }
       }
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) zk[k] = gelu_erf_(zk[k]);
+      for (int k = 0; k < VEC; ++k) zk[k] = dfno_gelu::gelu(zk[k]);
 #pragma unroll
       for (int o = 0; o < O2MAX; ++o) {
         if (o < O2) {
@@ -158,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           if (!full && k >= nv) break;
-          ph_st(ob + (long)o * S + k, acc[o][k]);
+          st(ob + (long)o * S + k, acc[o][k]);
         }
       }
           }
@@ -211,7 +188,7 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_fwd_fused_kernel(
       if (r >= IT * TS) break;
       const int row = r / TS;
       const int c = r - row * TS;
-      pf[q] = (c < nv) ? ph_ld(x + ((long)b * IT + row) * S + s0 + c) : 0.f;
+      pf[q] = (c < nv) ? ld(x + ((long)b * IT + row) * S + s0 + c) : 0.f;
     }
   };
   prefetch(blockIdx.x);
@@ -258,10 +235,10 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_fwd_fused_kernel(
       for (int k = 0; k < TS / 8; ++k) {
         const int c4 = half + k * 8;
         float4 zv = *reinterpret_cast<float4*>(ht + jj * LD + c4);
-        zv.x = gelu_erf_(zv.x + bj);
-        zv.y = gelu_erf_(zv.y + bj);
-        zv.z = gelu_erf_(zv.z + bj);
-        zv.w = gelu_erf_(zv.w + bj);
+        zv.x = dfno_gelu::gelu(zv.x + bj);
+        zv.y = dfno_gelu::gelu(zv.y + bj);
+        zv.z = dfno_gelu::gelu(zv.z + bj);
+        zv.w = dfno_gelu::gelu(zv.w + bj);
         *reinterpret_cast<float4*>(ht + jj * LD + c4) = zv;
       }
     }
@@ -283,7 +260,7 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_fwd_fused_kernel(
       if (kg == 0 && sc < S) {
 #pragma unroll
         for (int r = 0; r < O2T; ++r)
-          ph_st(out + ((long)b * O2T + r) * S + sc, c4[r] + b4[r]);
+          st(out + ((long)b * O2T + r) * S + sc, c4[r] + b4[r]);
       }
     }
   }
@@ -540,8 +517,8 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
       const int c = r - row * TS;
       float v = 0.f;
       if (c < nv) {
-        v = (row < IT) ? ph_ld(x + ((long)b * IT + row) * S + s0 + c)
-                       : ph_ld(gy + ((long)b * O2T + (row - IT)) * S + s0 + c);
+        v = (row < IT) ? ld(x + ((long)b * IT + row) * S + s0 + c)
+                       : ld(gy + ((long)b * O2T + (row - IT)) * S + s0 + c);
       }
       pf[q] = v;
     }
@@ -655,7 +632,7 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = mt * 16 + kg * 4 + r;
-          if (i < IT) ph_st(gx + ((long)b * IT + i) * S + sc, c4[r]);
+          if (i < IT) st(gx + ((long)b * IT + i) * S + sc, c4[r]);
         }
       }
     }
@@ -704,21 +681,6 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
     if (gW4s[k] != 0.f) atomicAdd(&gW4[k], gW4s[k]);
 }
 
-int grid_for_p(long work) {
-  long g = (work + kBlock - 1) / kBlock;
-  long cap = 256L * 8;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-void check_pf(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kDouble,
-              name, " must be float32/float64");
-}
-
 template <typename T>
 bool vec_ok(long S, std::initializer_list<const void*> ptrs) {
   if (!std::is_same<T, float>::value) return false;
@@ -734,7 +696,7 @@ at::Tensor proj_head_fwd(const at::Tensor& x, const at::Tensor& W3,
                          const at::Tensor& b3, const at::Tensor& W4,
                          const at::Tensor& b4) {
   const bool bf16 = x.scalar_type() == at::kBFloat16;
-  if (!bf16) { check_pf(x, "x"); }
+  if (!bf16) { check_real(x, "x"); }
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "x must be contiguous GPU");
   TORCH_CHECK(x.dim() == 3, "x must be [B,I,S]");
   int B = (int)x.size(0), I = (int)x.size(1);
@@ -746,7 +708,7 @@ at::Tensor proj_head_fwd(const at::Tensor& x, const at::Tensor& W3,
   auto out = at::empty({B, O2, S}, x.options());
   if (x.numel() == 0) return out;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = grid_for_p((long)B * ((S + 3) / 4));
+  int grid = launch_grid((long)B * ((S + 3) / 4), kBlock, 256L * 8);
   // The tiled-MFMA forward below is correct but measured SLOWER than the
   // register-resident per-thread kernel (1.48 vs 1.06 ms within-process
   // A/B at the flagship): the z3 tile costs 4 LDS passes + 3 barriers
@@ -811,8 +773,8 @@ at::Tensor proj_head_fwd(const at::Tensor& x, const at::Tensor& W3,
     DFNO_CHECK_LAUNCH("proj_head");
     return out;
   }
-  check_pf(W3, "W3"); check_pf(b3, "b3");
-  check_pf(W4, "W4"); check_pf(b4, "b4");
+  check_real(W3, "W3"); check_real(b3, "b3");
+  check_real(W4, "W4"); check_real(b4, "b4");
 
 #define PH_LAUNCH_FT(V)                                                       \
     hipLaunchKernelGGL((proj_head_fwd_kernel<scalar_t, IM, OM, 4, V, 128, 20>), \
@@ -850,8 +812,8 @@ at::Tensor proj_head_fwd(const at::Tensor& x, const at::Tensor& W3,
 std::vector<at::Tensor> proj_head_bwd(const at::Tensor& gy, const at::Tensor& x,
                                       const at::Tensor& W3, const at::Tensor& b3,
                                       const at::Tensor& W4) {
-  check_pf(gy, "gy"); check_pf(x, "x"); check_pf(W3, "W3");
-  check_pf(b3, "b3"); check_pf(W4, "W4");
+  check_real(gy, "gy"); check_real(x, "x"); check_real(W3, "W3");
+  check_real(b3, "b3"); check_real(W4, "W4");
   int B = (int)x.size(0), I = (int)x.size(1);
   long S = x.size(2);
   int M = (int)W3.size(0), O2 = (int)W4.size(0);
@@ -864,7 +826,7 @@ std::vector<at::Tensor> proj_head_bwd(const at::Tensor& gy, const at::Tensor& x,
   if (x.numel() == 0) return {gz3, gb3, gW4, gb4};
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = grid_for_p((long)B * ((S + 3) / 4));
+  int grid = launch_grid((long)B * ((S + 3) / 4), kBlock, 256L * 8);
 
 #define PH_LAUNCH_BT(V)                                                       \
     hipLaunchKernelGGL((proj_head_bwd_kernel<scalar_t, IM, OM, 4, V, 128, 20>), \
@@ -923,7 +885,7 @@ std::vector<at::Tensor> proj_head_bwd_fused(const at::Tensor& gy,
   auto W3f = bf16 ? W3.to(at::kFloat).contiguous() : W3;
   auto b3f = bf16 ? b3.to(at::kFloat).contiguous() : b3;
   auto W4f = bf16 ? W4.to(at::kFloat).contiguous() : W4;
-  check_pf(W3f, "W3"); check_pf(b3f, "b3"); check_pf(W4f, "W4");
+  check_real(W3f, "W3"); check_real(b3f, "b3"); check_real(W4f, "W4");
   auto fopt = x.options().dtype(at::kFloat);   // weight grads accumulate fp32
   auto gx = at::empty({B, I, S}, x.options());
   auto gW3 = at::zeros({M, I}, fopt);

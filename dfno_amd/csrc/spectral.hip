@@ -24,8 +24,11 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include "kernels.h"
+#include "device_util.h"
 
 namespace {
+
+using namespace dfno_io;
 
 constexpr int kBlock = 256;
 constexpr int kMaxDims = 6;
@@ -317,13 +320,6 @@ __global__ __launch_bounds__(kBlock) void spectral_corners_bwd_w_kernel(
   }
 }
 
-int grid_for_s(long work) {
-  long g = (work + kBlock - 1) / kBlock;
-  long cap = 256L * 16;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 BoxGeom make_geom(const at::Tensor& x, const at::Tensor& w,
                   const std::vector<int64_t>& starts) {
@@ -373,7 +369,7 @@ void spectral_corner_fwd(const at::Tensor& x, const at::Tensor& w, at::Tensor& y
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   constexpr int OT = 8;
   long ntiles = (O + OT - 1) / OT;
-  int grid = grid_for_s(g.nelem * ntiles * B);
+  int grid = launch_grid(g.nelem * ntiles * B, kBlock, 256L * 16);
 
   if (x.scalar_type() == at::kComplexFloat) {
     hipLaunchKernelGGL((spectral_corner_kernel<float, OT, false>), dim3(grid),
@@ -403,7 +399,7 @@ void spectral_corner_bwd_x(const at::Tensor& gy, const at::Tensor& w, at::Tensor
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   constexpr int OT = 8;
   long ntiles = (I + OT - 1) / OT;
-  int grid = grid_for_s(g.nelem * ntiles * B);
+  int grid = launch_grid(g.nelem * ntiles * B, kBlock, 256L * 16);
 
   if (gy.scalar_type() == at::kComplexFloat) {
     hipLaunchKernelGGL((spectral_corner_kernel<float, OT, true>), dim3(grid),
@@ -493,7 +489,7 @@ static void launch_corners(const at::Tensor& x,
       ++idx;
     }
     if (mg.ncorners == 0) continue;
-    int grid = grid_for_s(mg.cum[mg.ncorners] * B);
+    int grid = launch_grid(mg.cum[mg.ncorners] * B, kBlock, 256L * 16);
     const int n_in = CONJT ? O : I;
 #define SPC_LAUNCH(NINV)                                                       \
     hipLaunchKernelGGL((spectral_corners_kernel<T, OT, CONJT, NINV, FP8>),     \
@@ -655,7 +651,7 @@ void spectral_corners_bwd_w(const at::Tensor& x, const at::Tensor& gy,
         ++idx;                                                                 \
       }                                                                        \
       if (mg.ncorners == 0) continue;                                          \
-      int grid = grid_for_s(mg.cum[mg.ncorners] * O);                          \
+      int grid = launch_grid(mg.cum[mg.ncorners] * O, kBlock, 256L * 16);      \
       hipLaunchKernelGGL((spectral_corners_bwd_w_kernel<T, ICAP_>),            \
                          dim3(grid), dim3(kBlock), 0, stream,                  \
                          reinterpret_cast<const T*>(x.data_ptr()),             \

@@ -1,6 +1,6 @@
 """bf16 compute-config tests (BASELINE.json config #2).
 
-Native bf16-storage kernels (csrc/bf16.hip: fp32 arithmetic, bf16 IO) are
+Native bf16-storage kernels (fp32 arithmetic, bf16 IO) are
 checked against plain fp32 torch references at bf16 tolerances, and the full
 bf16 model fwd+bwd is compared against the fp32 model with identical weights.
 """
@@ -62,6 +62,55 @@ def test_bf16_channel_mix_transposed():
     gx, _ = ext.bf16_channel_mix(gz, W, empty, False, True, False, empty)
     ref = torch.einsum("oi,bos->bis", W.float(), gz.float())
     assert torch.allclose(gx.float(), ref, rtol=BT, atol=BT)
+
+
+@pytest.mark.parametrize("B,I,O,S,act,bias,res,wt", [
+    # generic (not compile-time-pinned) instantiations, one per table row
+    (1, 3, 5, 8, True, True, False, False),       # x-resident cap 8, VEC 8
+    (2, 12, 7, 264, True, True, False, False),    # x-resident cap 24, VEC 4
+    (1, 32, 3, 264, False, False, False, False),  # x-resident cap 32
+    (2, 40, 8, 8, True, True, False, False),      # acc-resident cap 8, VEC 8
+    (1, 40, 24, 264, False, True, False, False),  # acc-resident cap 24, VEC 4
+    # residual: added after the i-sum, before z is stored
+    (2, 12, 7, 264, True, False, True, False),
+    (1, 40, 8, 264, True, True, True, False),     # acc-resident with residual
+    # transposed weights on a non-square shape
+    (1, 12, 7, 264, False, False, False, True),
+])
+def test_bf16_channel_mix_generic(B, I, O, S, act, bias, res, wt):
+    ext = _ext()
+    torch.manual_seed(4)
+    x = (torch.rand(B, I, S, device="cuda") - 0.5).bfloat16()
+    # W is [out, in]; wt=True hands the kernel the [in, out] storage
+    W = ((torch.rand(O, I, device="cuda") - 0.5) / I).bfloat16()
+    empty = torch.empty(0, dtype=torch.bfloat16, device="cuda")
+    b = (torch.rand(O, device="cuda") - 0.5).bfloat16() if bias else empty
+    r = (torch.rand(B, O, S, device="cuda") - 0.5).bfloat16() if res else empty
+    y, z = ext.bf16_channel_mix(x, W.t().contiguous() if wt else W, b, act, wt,
+                                act, r)
+    assert y.shape == (B, O, S) and y.dtype == torch.bfloat16
+
+    zr = torch.einsum("oi,bis->bos", W.float(), x.float())
+    if bias:
+        zr = zr + b.float().view(1, -1, 1)
+    if res:
+        zr = zr + r.float()
+    yr = F.gelu(zr) if act else zr
+    assert torch.allclose(y.float(), yr, rtol=BT, atol=BT), \
+        f"max {(y.float()-yr).abs().max()}"
+    if act:
+        assert torch.allclose(z.float(), zr, rtol=BT, atol=BT)
+
+
+@pytest.mark.parametrize("I,O,S", [(20, 20, 12), (40, 30, 64)])
+def test_bf16_channel_mix_unsupported_raises(I, O, S):
+    """S must be a multiple of 8, and I > 32 needs O <= 24: no fallback."""
+    ext = _ext()
+    x = torch.zeros(1, I, S, device="cuda", dtype=torch.bfloat16)
+    W = torch.zeros(O, I, device="cuda", dtype=torch.bfloat16)
+    empty = torch.empty(0, dtype=torch.bfloat16, device="cuda")
+    with pytest.raises(RuntimeError, match="bf16 channel mix"):
+        ext.bf16_channel_mix(x, W, empty, False, False, False, empty)
 
 
 def test_bf16_grad_w():

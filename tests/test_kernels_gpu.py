@@ -122,31 +122,64 @@ def test_channel_mix_bwd_w(ext, dtype, B, I, O, S, bias):
         assert torch.allclose(gb, refb, **t)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("B,I,O,S", [
+    (2, 20, 20, 1003),  # the pinned block shape, odd S (element-wise tail)
+    (1, 7, 9, 64),       # generic cap-8 kernel, float4 path in fp32
+])
+def test_linear_res_gelu_fwd(ext, dtype, B, I, O, S):
+    """y = gelu(z), z = W x + res: the x-resident mix with its residual."""
+    torch.manual_seed(4)
+    x = torch.randn(B, I, S, device="cuda", dtype=dtype)
+    W = torch.randn(O, I, device="cuda", dtype=dtype) / math.sqrt(I)
+    res = torch.randn(B, O, S, device="cuda", dtype=dtype)
+    y, z = ext.linear_res_gelu_fwd(x, W, res)
+    z_ref = torch.einsum("oi,bis->bos", W, x) + res
+    assert torch.allclose(z, z_ref, **tol(dtype)), f"max {(z - z_ref).abs().max()}"
+    assert torch.allclose(y, F.gelu(z_ref), **tol(dtype)), \
+        f"max {(y - F.gelu(z_ref)).abs().max()}"
+
+
 # ---------------------------------------------------------------------------
 # gelu / add+gelu
 # ---------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n", [1, 17, 4096, 100003])
-def test_gelu_fwd_bwd(ext, n):
-    torch.manual_seed(2)
-    x = torch.randn(n, device="cuda") * 3
-    y = ext.gelu_fwd(x)
-    assert torch.allclose(y, F.gelu(x), rtol=1e-5, atol=1e-6)
+def _elementwise_tol(dtype):
+    # fp32: the rational-erf GELU is good to 1e-5 relative; fp64 calls erf
+    return dict(rtol=1e-5, atol=1e-6) if dtype == torch.float32 else tol(dtype)
 
-    gy = torch.randn(n, device="cuda")
+
+@pytest.mark.parametrize("n", [1, 17, 4096, 100003])
+def test_gelu_fwd_bwd(ext, n, dtype=torch.float32):
+    t = _elementwise_tol(dtype)
+    torch.manual_seed(2)
+    x = torch.randn(n, device="cuda", dtype=dtype) * 3
+    y = ext.gelu_fwd(x)
+    assert torch.allclose(y, F.gelu(x), **t)
+
+    gy = torch.randn(n, device="cuda", dtype=dtype)
     gz = ext.gelu_bwd(gy, x)
     xr = x.clone().requires_grad_(True)
     F.gelu(xr).backward(gy)
-    assert torch.allclose(gz, xr.grad, rtol=1e-5, atol=1e-6)
+    assert torch.allclose(gz, xr.grad, **t)
 
 
-def test_add_gelu(ext):
+def test_gelu_fwd_bwd_fp64(ext):
+    test_gelu_fwd_bwd(ext, 17, torch.float64)
+
+
+def test_add_gelu(ext, shape=(2, 5, 333), dtype=torch.float32):
+    t = _elementwise_tol(dtype)
     torch.manual_seed(3)
-    a = torch.randn(2, 5, 333, device="cuda")
-    b = torch.randn(2, 5, 333, device="cuda")
+    a = torch.randn(*shape, device="cuda", dtype=dtype)
+    b = torch.randn(*shape, device="cuda", dtype=dtype)
     y, z = ext.add_gelu_fwd(a, b)
     assert torch.allclose(z, a + b)
-    assert torch.allclose(y, F.gelu(a + b), rtol=1e-5, atol=1e-6)
+    assert torch.allclose(y, F.gelu(a + b), **t)
+
+
+def test_add_gelu_fp64(ext):
+    test_add_gelu(ext, (17,), torch.float64)
 
 
 # ---------------------------------------------------------------------------
@@ -589,10 +622,9 @@ def test_fused_adam_matches_torch():
 # ---------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype,tt", [(torch.float32, 3e-4), (torch.float64, 1e-10)])
-def test_lift_head(dtype, tt):
+def test_lift_head(dtype, tt, B=1, C=2, S=5000, Tn=30, W=20):
     from dfno_amd.ops import lift_head
     torch.manual_seed(21)
-    B, C, S, Tn, W = 1, 2, 5000, 30, 20
     x = torch.randn(B, C, S, 1, device="cuda", dtype=dtype, requires_grad=True)
     W1 = torch.randn(Tn, 1, device="cuda", dtype=dtype).requires_grad_(True)
     b1 = torch.randn(Tn, device="cuda", dtype=dtype).requires_grad_(True)
@@ -617,3 +649,12 @@ def test_lift_head(dtype, tt):
     for a, b in [(x, xr), (W1, W1r), (b1, b1r), (W2, W2r), (b2, b2r)]:
         assert torch.allclose(a.grad, b.grad, rtol=tt * 30, atol=tt * 30), \
             f"grad max {(a.grad-b.grad).abs().max()}"
+
+
+@pytest.mark.parametrize("C,Tn,W,S", [
+    (4, 32, 24, 5),      # every cap at once, fewer points than one wave
+    (1, 9, 20, 300),     # off the caps, pinned width, more than one block
+])
+def test_lift_head_fp64_single_step(C, Tn, W, S):
+    """fp64 with T_in == 1 runs the chunked general-lift kernels."""
+    test_lift_head(torch.float64, 1e-10, 1, C, S, Tn, W)
