@@ -132,7 +132,7 @@ def main():
 
 
 if __name__ == "__main__":
-    if "--dft" not in sys.argv and "--lift" not in sys.argv:
+    if not {"--dft", "--lift", "--wide"} & set(sys.argv):
         main()
 
 
@@ -167,12 +167,15 @@ if "__main__" == __name__ and "--dft" in sys.argv:
     dft_bench()
 
 
-def _alternate(fns, rounds=5, iters=50):
-    """Time each fn in turn, `rounds` times over; median seconds per call."""
+def _alternate(fns, rounds=5, iters=50, all_rounds=False):
+    """Time each fn in turn, `rounds` times over; median seconds per call
+    (every round's time per fn with ``all_rounds``)."""
     times = [[] for _ in fns]
     for _ in range(rounds):
         for i, fn in enumerate(fns):
             times[i].append(bench(fn, iters=iters, warmup=5))
+    if all_rounds:
+        return times
     return [sorted(t)[len(t) // 2] for t in times]
 
 
@@ -256,3 +259,59 @@ def lift_model_bench():
 if "__main__" == __name__ and "--lift" in sys.argv:
     lift_bench()
     lift_model_bench()
+
+
+def wide_bench():
+    """Wide channel mix (mix_wide.hip) at I = O = 64, B = 1, S = 64^3 * 30,
+    fp32 and bf16.  The plain bias+GELU form runs against what served the
+    shape before (the scalar LDS kernel behind channel_mix_fwd in fp32, the
+    einsum composition in bf16), alternating, five rounds: the new kernel's
+    slowest round has to beat the old route's fastest.  The residual+GELU
+    form had no native route; it reports time and TB/s on x, res, y, z."""
+    import torch.nn.functional as F
+
+    S, C = 64 * 64 * 64 * 30, 64
+    for dtype in (torch.float32, torch.bfloat16):
+        torch.manual_seed(0)
+        es = 4 if dtype == torch.float32 else 2
+        name = str(dtype).split(".")[-1]
+        x = torch.randn(1, C, S, device="cuda", dtype=dtype)
+        W = (torch.randn(C, C, device="cuda") / 8).to(dtype)
+        b = torch.randn(C, device="cuda").to(dtype)
+        e = torch.empty(0, device="cuda", dtype=dtype)
+
+        def wide_plain():
+            return ext.wide_channel_mix(x, W, b, e, True, False, True)
+
+        if dtype == torch.float32:
+            def old_plain():
+                return ext.channel_mix_fwd(x, W, b, True)
+        else:
+            def old_plain():
+                z = torch.einsum("oi,bis->bos", W, x) + b.view(1, -1, 1)
+                return F.gelu(z), z
+
+        tn, to = _alternate([wide_plain, old_plain], iters=10, all_rounds=True)
+        nbytes = 3 * C * S * es                      # x, y, z
+        report(f"wide mix bias+gelu {name} (median)", sorted(tn)[2], nbytes)
+        report(f"old route bias+gelu {name} (median)", sorted(to)[2], nbytes)
+        print(f"  wide rounds ms {[round(t * 1e3, 3) for t in tn]}  "
+              f"old rounds ms {[round(t * 1e3, 3) for t in to]}  "
+              f"slowest wide < fastest old: {max(tn) < min(to)}")
+        del to
+
+        res = torch.randn(1, C, S, device="cuda", dtype=dtype)
+        (tr,) = _alternate([lambda: ext.wide_channel_mix(x, W, e, res, True,
+                                                         False, True)], iters=10)
+        report(f"wide mix res+gelu (x,res,y,z) {name}", tr, 4 * C * S * es)
+        (tq,) = _alternate([lambda: ext.wide_channel_mix(x, W, e, res, True,
+                                                         False, False)], iters=10)
+        report(f"wide mix res+gelu, no z (x,res,y) {name}", tq, 3 * C * S * es)
+        (tt,) = _alternate([lambda: ext.wide_channel_mix(x, W, e, e, False,
+                                                         True, False)], iters=10)
+        report(f"wide mix transposed (gz,gx) {name}", tt, 2 * C * S * es)
+        del res
+
+
+if "__main__" == __name__ and "--wide" in sys.argv:
+    wide_bench()

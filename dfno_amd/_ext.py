@@ -35,6 +35,7 @@ SOURCES = [
     _CSRC / "dft2d.hip",
     _CSRC / "mix_bwd.hip",
     _CSRC / "epilogue.hip",
+    _CSRC / "mix_wide.hip",
 ]
 
 

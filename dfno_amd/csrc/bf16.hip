@@ -34,7 +34,7 @@ constexpr int kVec = 8;   // bf16 per lane per vector op (16 B)
 // per pair at thread end.
 // ---------------------------------------------------------------------------
 
-template <int NP>
+template <int NP, int XR = 32>
 __global__ __launch_bounds__(kBlock) void bf16_gw_kernel(
     const unsigned short* __restrict__ gz, const unsigned short* __restrict__ x,
     float* __restrict__ gW, float* __restrict__ gb,
@@ -47,8 +47,8 @@ __global__ __launch_bounds__(kBlock) void bf16_gw_kernel(
                                    // 4 blocks/CU stay resident (the O=128
                                    // single-slab version ran 1 block/CU)
   extern __shared__ __align__(16) char smem_raw[];
-  float* xs = reinterpret_cast<float*>(smem_raw);    // [I][LD]
-  float* gs = xs + (size_t)32 * LD;                  // [O_sl][LD]
+  float* xs = reinterpret_cast<float*>(smem_raw);    // [I <= XR][LD]
+  float* gs = xs + (size_t)XR * LD;                  // [O_sl][LD]
 
   const int o0 = (int)blockIdx.y * OSL;
   const int O_sl = min(OSL, O - o0);
@@ -218,7 +218,7 @@ std::vector<at::Tensor> bf16_channel_mix_bwd_w(const at::Tensor& gz,
   const int I = (int)x.size(1);
   const long S = x.size(2);
   const int O = (int)gz.size(1);
-  TORCH_CHECK(I <= 32, "bf16 grad-W: I must be <= 32");
+  TORCH_CHECK(I <= 64, "bf16 grad-W: I must be <= 64");
   TORCH_CHECK(O <= 128, "bf16 grad-W: O must be <= 128");
   TORCH_CHECK(S % 128 == 0, "bf16 grad-W: S must be a multiple of 128");
 
@@ -233,7 +233,7 @@ std::vector<at::Tensor> bf16_channel_mix_bwd_w(const at::Tensor& gz,
     return e && e[0] == '1';
   }();
   const int mfma_pairs = ((O + 15) / 16) * ((I + 15) / 16);
-  if (!no_mfma && S % 256 == 0 && mfma_pairs <= 16) {
+  if (!no_mfma && S % 256 == 0 && mfma_pairs <= 32) {
     long ntiles = (S / 256) * (long)B;
     int grid = (int)std::min(ntiles, 2048L);
     if (mfma_pairs <= 4) {
@@ -241,8 +241,13 @@ std::vector<at::Tensor> bf16_channel_mix_bwd_w(const at::Tensor& gz,
                          stream, usp(gz), usp(x), gW.data_ptr<float>(),
                          gb.numel() ? gb.data_ptr<float>() : nullptr, B, I, O,
                          S, want_bias);
-    } else {
+    } else if (mfma_pairs <= 16) {
       hipLaunchKernelGGL((bf16_gw_mfma_kernel<4>), dim3(grid), dim3(kBlock), 0,
+                         stream, usp(gz), usp(x), gW.data_ptr<float>(),
+                         gb.numel() ? gb.data_ptr<float>() : nullptr, B, I, O,
+                         S, want_bias);
+    } else {   // 33..64 x rows against up to 128 gz rows
+      hipLaunchKernelGGL((bf16_gw_mfma_kernel<8>), dim3(grid), dim3(kBlock), 0,
                          stream, usp(gz), usp(x), gW.data_ptr<float>(),
                          gb.numel() ? gb.data_ptr<float>() : nullptr, B, I, O,
                          S, want_bias);
@@ -253,7 +258,8 @@ std::vector<at::Tensor> bf16_channel_mix_bwd_w(const at::Tensor& gz,
   constexpr int LD = 132;
   const int nslab = (O + 31) / 32;
   const int o_sl = std::min(O, 32);
-  size_t smem = sizeof(float) * (size_t)(32 + o_sl) * LD;
+  const int xr = I <= 32 ? 32 : 64;
+  size_t smem = sizeof(float) * (size_t)(xr + o_sl) * LD;
   long ntiles = (S / 128) * (long)B;
   int grid = (int)std::min(ntiles, 2048L);
   const int pairs = o_sl * I;
@@ -262,7 +268,12 @@ std::vector<at::Tensor> bf16_channel_mix_bwd_w(const at::Tensor& gz,
                      smem, stream, usp(gz), usp(x), gW.data_ptr<float>(),      \
                      gb.numel() ? gb.data_ptr<float>() : nullptr, B, I, O, S,  \
                      want_bias);
-  if (pairs <= 256) { BGW(1) } else if (pairs <= 512) { BGW(2) }
+  if (I > 32) {
+    hipLaunchKernelGGL((bf16_gw_kernel<8, 64>), dim3(grid, nslab), dim3(kBlock),
+                       smem, stream, usp(gz), usp(x), gW.data_ptr<float>(),
+                       gb.numel() ? gb.data_ptr<float>() : nullptr, B, I, O, S,
+                       want_bias);
+  } else if (pairs <= 256) { BGW(1) } else if (pairs <= 512) { BGW(2) }
   else { BGW(4) }
 #undef BGW
   DFNO_CHECK_LAUNCH("bf16_gw");

@@ -13,6 +13,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "split-s grad-W (+grad-bias) reduction");
   m.def("linear_res_gelu_fwd", &linear_res_gelu_fwd,
         "fused y = gelu(W @ x + res): returns (y, z)");
+  m.def("wide_channel_mix", &wide_channel_mix,
+        "MFMA channel mix for 33 <= max(I, O) <= 128 (+bias/res/gelu, "
+        "optionally transposed): returns (y, z)");
   m.def("irfft_linear_res_gelu_fwd", &irfft_linear_res_gelu_fwd,
         "fused y = gelu(W @ x + pad_irfft(Yt)): returns (y, z)");
   m.def("rfft_adj_mix", &rfft_adj_mix,

@@ -37,15 +37,20 @@ constexpr int kBlock = 256;
 constexpr int kMaxN = 64;    // cap of the fully-tuned N<=64 paths
 constexpr int kMaxNBig = 256;  // cap of the generalized radix-8xNB / LB paths
 
-template <typename T>
-__device__ __forceinline__ void sincos_t(T a, T* s, T* c);
-template <>
-__device__ __forceinline__ void sincos_t<float>(float a, float* s, float* c) {
-  sincosf(a, s, c);
+// The recurrence step of kept mode k, w^{sgn k} = exp(sgn 2 pi i k / N).  The
+// angle is reduced to |k'| <= N/2 (k' = k - N for the suffix modes) and taken
+// in units of pi, so its only rounding is that of 2 k' / N (none when N is a
+// power of two).  sincosf of the unreduced float(2 pi k / N) is off by up to
+// 4e-7 for k near N and the recurrence multiplies that by j: with a dominant
+// DC term the k = N - 1 bin of an N = 8 transform came out 4e-6 wrong where
+// the table-driven kernels are at 2e-7.
+__device__ __forceinline__ void mode_step(int k, int N, float sgn, float* s, float* c) {
+  const int kr = (2 * k > N) ? k - N : k;
+  sincospif(sgn * (float)(2 * kr) / (float)N, s, c);
 }
-template <>
-__device__ __forceinline__ void sincos_t<double>(double a, double* s, double* c) {
-  *s = sin(a); *c = cos(a);
+__device__ __forceinline__ void mode_step(int k, int N, double sgn, double* s, double* c) {
+  const int kr = (2 * k > N) ? k - N : k;
+  sincospi(sgn * (double)(2 * kr) / (double)N, s, c);
 }
 
 // Per-mode twiddle recurrence: each kept mode ki keeps its current factor
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_analysis_kernel(
   for (int ki = 0; ki < MCAP; ++ki) {
     if (ki < m) {
       int k = kept_k(ki, m_lo, N, m_hi);
-      sincos_t<T>(T(-2.0) * T(M_PI) * T(k) / T(N), &sti[ki], &str[ki]);
+      mode_step(k, N, T(-1), &sti[ki], &str[ki]);
     }
   }
 
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_synthesis_kernel(
   for (int ki = 0; ki < MCAP; ++ki) {
     if (ki < m) {
       int k = kept_k(ki, m_lo, N, m_hi);
-      sincos_t<T>(T(2.0) * T(M_PI) * T(k) / T(N), &sti[ki], &str[ki]);
+      mode_step(k, N, T(1), &sti[ki], &str[ki]);
     }
   }
 

@@ -27,6 +27,14 @@ at::Tensor channel_mix_fwd_t(const at::Tensor& gz, const at::Tensor& W);
 std::vector<at::Tensor> linear_res_gelu_fwd(const at::Tensor& x, const at::Tensor& W,
                                             const at::Tensor& res);
 
+// wide channel mix (mix_wide.hip), 33 <= max(I, O) <= 128, fp32 or bf16
+// storage: y = act(W x + b + res) with x [B,I,S]; wt contracts over W's rows
+// instead (gx = W^T gz, W left as [O,I]).  b / res may be empty.  Returns
+// {y, z}; z (the pre-activation) is empty and never written unless need_z.
+std::vector<at::Tensor> wide_channel_mix(const at::Tensor& x, const at::Tensor& W,
+                                         const at::Tensor& b, const at::Tensor& res,
+                                         bool act, bool wt, bool need_z);
+
 // fused block epilogue with the time-axis irfft synthesized on the fly
 // (epilogue.hip): z = W @ x + pad_irfft(Yt, n_out), y = gelu(z), with
 // x [B,I,S] fp32, Yt [B,O,L,m] complex64, S = L * n_out.  Returns {y, z};
@@ -69,7 +77,7 @@ std::vector<at::Tensor> proj_head_bwd_fused(const at::Tensor& gy,
                                             const at::Tensor& W4);
 
 // split-s outer-product reduction: gW[o,i] = sum_{b,s} gz[b,o,s] x[b,i,s]
-// (+ gb[o] = sum gz when want_bias); requires I <= 32.
+// (+ gb[o] = sum gz when want_bias); requires I <= 64.
 std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor& x,
                                           bool want_bias);
 

@@ -734,14 +734,18 @@ std::vector<at::Tensor> bf16_add_gelu(const at::Tensor& a, const at::Tensor& b) 
 
 namespace {
 
-template <typename T, int ICAP, int OW, bool BIAS, bool VECTOR>
+template <typename T, int ICAP, int OW, bool BIAS, bool VECTOR, bool ISLAB = false>
 __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
     const T* __restrict__ A, const T* __restrict__ Bm,
     T* __restrict__ gW, T* __restrict__ gb,
-    int B, int O, int I, long S, int n_schunk) {
+    int B, int O, int I_, long S, int n_schunk) {
   // grid: blockIdx.x = schunk * o_tiles + o_tile (s-chunk-major); each wave
   // owns OW consecutive output rows (cuts B re-reads by OW and raises the
-  // fma:load ratio).
+  // fma:load ratio).  ISLAB (I_ > ICAP): blockIdx.y picks the slab of ICAP
+  // B rows this block reduces; slab 0 owns the bias.
+  const int i0 = ISLAB ? (int)blockIdx.y * ICAP : 0;
+  const int I = ISLAB ? min(ICAP, I_ - i0) : I_;   // rows of this slab
+  const bool do_bias = BIAS && (!ISLAB || blockIdx.y == 0);
   const int o_tiles = (O + 4 * OW - 1) / (4 * OW);
   const int schunk = blockIdx.x / o_tiles;
   const int o_tile = blockIdx.x % o_tiles;
@@ -766,7 +770,7 @@ __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
   if (o0 < O) {
     for (int b = 0; b < B; ++b) {
       const T* Ab = A + ((long)b * O + o0) * S;
-      const T* Bb = Bm + ((long)b * I) * S;
+      const T* Bb = Bm + ((long)b * I_ + i0) * S;
       if constexpr (VECTOR && std::is_same<T, float>::value) {
         const long tail0 = s0 + ((s1 - s0) / (64 * 4)) * (64 * 4);
         for (long s = s0 + (long)lane * 4; s < tail0; s += 64 * 4) {
@@ -775,7 +779,7 @@ __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
           for (int w = 0; w < OW; ++w) {
             if (o0 + w < O) {
               av[w] = *reinterpret_cast<const float4*>(Ab + (long)w * S + s);
-              if (BIAS) bacc[w] += av[w].x + av[w].y + av[w].z + av[w].w;
+              if (do_bias) bacc[w] += av[w].x + av[w].y + av[w].z + av[w].w;
             }
           }
 #pragma unroll
@@ -796,7 +800,7 @@ __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
           for (int w = 0; w < OW; ++w) {
             if (o0 + w < O) {
               T av = Ab[(long)w * S + s];
-              if (BIAS) bacc[w] += av;
+              if (do_bias) bacc[w] += av;
 #pragma unroll
               for (int i = 0; i < ICAP; ++i)
                 if (i < I) acc[w][i] += av * Bb[(long)i * S + s];
@@ -809,7 +813,7 @@ __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
           for (int w = 0; w < OW; ++w) {
             if (o0 + w < O) {
               T av = Ab[(long)w * S + s];
-              if (BIAS) bacc[w] += av;
+              if (do_bias) bacc[w] += av;
 #pragma unroll
               for (int i = 0; i < ICAP; ++i)
                 if (i < I) acc[w][i] += av * Bb[(long)i * S + s];
@@ -828,10 +832,10 @@ __global__ __launch_bounds__(kBlock) void gw_outer_kernel(
       for (int i = 0; i < ICAP; ++i) {
         if (i < I) {
           T v = wave_sum(acc[w][i]);
-          if (lane == 0 && v != T(0)) atomicAdd(&gW[(size_t)(o0 + w) * I + i], v);
+          if (lane == 0 && v != T(0)) atomicAdd(&gW[(size_t)(o0 + w) * I_ + i0 + i], v);
         }
       }
-      if (BIAS) {
+      if (do_bias) {
         T v = wave_sum(bacc[w]);
         if (lane == 0 && v != T(0)) atomicAdd(&gb[o0 + w], v);
       }
@@ -1066,20 +1070,24 @@ namespace {
 
 typedef float f32x4_pw __attribute__((ext_vector_type(4)));
 
-template <int NPAIR>
+template <int NPAIR, int XR = 32, int OSL = 64, bool BIAS = false>
 __global__ __launch_bounds__(kBlock) void gw_mfma_f32_kernel(
     const float* __restrict__ gz, const float* __restrict__ x,
-    float* __restrict__ gW, int B, int O, int I, long S) {
+    float* __restrict__ gW, int B, int O, int I, long S,
+    float* __restrict__ gb = nullptr) {
   constexpr int TS = 128;          // s per tile (32 MFMA K-steps)
   constexpr int LD = TS + 4;       // float4-aligned row pad
-  constexpr int OSL = 64;          // o-rows per blockIdx.y slab
+  // OSL: o-rows per blockIdx.y slab; XR: x-row capacity (I <= XR).  The
+  // I <= 64 instantiation halves the slab, keeping the tile pair near 50 KB.
+  // BIAS: B column I is a constant one, so D column I is gb (as in
+  // mix_bwd_fused); o-slabs partition the rows, each gb[o] has one owner.
   extern __shared__ __align__(16) char smem_raw[];
-  float* xs = reinterpret_cast<float*>(smem_raw);    // [I<=32][LD]
-  float* gs = xs + (size_t)32 * LD;                  // [O_sl][LD]
+  float* xs = reinterpret_cast<float*>(smem_raw);    // [I<=XR][LD]
+  float* gs = xs + (size_t)XR * LD;                  // [O_sl][LD]
 
   const int o0 = (int)blockIdx.y * OSL;
   const int O_sl = min(OSL, O - o0);
-  const int iT = (I + 15) / 16;
+  const int iT = (I + (BIAS ? 1 : 0) + 15) / 16;
   const int npairs = ((O_sl + 15) / 16) * iT;
 
   const int lane = (int)(threadIdx.x & 63);
@@ -1120,7 +1128,8 @@ __global__ __launch_bounds__(kBlock) void gw_mfma_f32_kernel(
 #pragma unroll
         for (int k = 0; k < TS; k += 4) {
           const float a = av ? gr[k + kg] : 0.f;
-          const float bb = bv ? xr[k + kg] : 0.f;
+          const float bb = bv ? xr[k + kg]
+                              : ((BIAS && nt * 16 + l16 == I) ? 1.f : 0.f);
           acc[pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, acc[pp], 0, 0, 0);
         }
       }
@@ -1137,8 +1146,10 @@ __global__ __launch_bounds__(kBlock) void gw_mfma_f32_kernel(
     for (int r = 0; r < 4; ++r) {
       const int o = o0 + mt * 16 + kg * 4 + r;   // D row
       const int i = nt * 16 + l16;               // D col
-      if (o < O && (mt * 16 + kg * 4 + r) < O_sl && i < I)
-        atomicAdd(&gW[(size_t)o * I + i], acc[pp][r]);
+      if (o < O && (mt * 16 + kg * 4 + r) < O_sl) {
+        if (i < I) atomicAdd(&gW[(size_t)o * I + i], acc[pp][r]);
+        else if (BIAS && i == I) atomicAdd(&gb[o], acc[pp][r]);
+      }
     }
   }
 }
@@ -1152,7 +1163,7 @@ std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor
   int B = (int)gz.size(0), O = (int)gz.size(1), I = (int)x.size(1);
   long S = gz.size(2);
   TORCH_CHECK(x.size(0) == B && x.size(2) == S, "shape mismatch");
-  TORCH_CHECK(I <= 32, "channel_mix_bwd_w: I must be <= 32");
+  TORCH_CHECK(I <= 64, "channel_mix_bwd_w: I must be <= 64");
 
   auto gW = at::zeros({O, I}, gz.options());
   auto gb = want_bias ? at::zeros({O}, gz.options())
@@ -1227,19 +1238,67 @@ std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor
   // big-O no-bias shapes (the projection lift's gW3 [128, 20]) take the
   // f32-MFMA tile kernel; identical numerics (f32-in MFMA is a bitwise
   // fmaf chain, cdna_hip_programming.md section 3)
-  if (is_f32 && vec && !no_mfma_gw && !want_bias && (long)O * I >= 1024 &&
-      I <= 32 && S % 128 == 0) {
+  if (is_f32 && vec && !no_mfma_gw && (!want_bias || I > 32) &&
+      (long)O * I >= 1024 && S % 128 == 0) {
     long ntiles = (S / 128) * (long)B;
-    int nslab = (O + 63) / 64;
-    int gx_ = (int)std::min(ntiles, (long)(256 * 3 / std::max(nslab, 1)));
-    size_t smem = sizeof(float) * (size_t)(32 + std::min(O, 64)) * 132;
-    hipLaunchKernelGGL((gw_mfma_f32_kernel<2>), dim3(gx_, nslab),
-                       dim3(kBlock), smem, stream, gz.data_ptr<float>(),
-                       x.data_ptr<float>(), gW.data_ptr<float>(), B, O,
-                       (int)I, S);
+    if (I <= 32) {
+      int nslab = (O + 63) / 64;
+      int gx_ = (int)std::min(ntiles, (long)(256 * 3 / std::max(nslab, 1)));
+      size_t smem = sizeof(float) * (size_t)(32 + std::min(O, 64)) * 132;
+      hipLaunchKernelGGL((gw_mfma_f32_kernel<2>), dim3(gx_, nslab),
+                         dim3(kBlock), smem, stream, gz.data_ptr<float>(),
+                         x.data_ptr<float>(), gW.data_ptr<float>(), B, O,
+                         (int)I, S, static_cast<float*>(nullptr));
+    } else {   // 33..64 x rows: 4 i-tiles x 2 o-tiles per 32-row slab
+      int nslab = (O + 31) / 32;
+      int gx_ = (int)std::min(ntiles, (long)(256 * 3 / std::max(nslab, 1)));
+      size_t smem = sizeof(float) * (size_t)(64 + std::min(O, 32)) * 132;
+      if (want_bias) {   // 2 o-tiles x (4 i-tiles + the ones column's)
+        hipLaunchKernelGGL((gw_mfma_f32_kernel<3, 64, 32, true>),
+                           dim3(gx_, nslab), dim3(kBlock), smem, stream,
+                           gz.data_ptr<float>(), x.data_ptr<float>(),
+                           gW.data_ptr<float>(), B, O, (int)I, S,
+                           gb.data_ptr<float>());
+      } else {
+        hipLaunchKernelGGL((gw_mfma_f32_kernel<2, 64, 32>), dim3(gx_, nslab),
+                           dim3(kBlock), smem, stream, gz.data_ptr<float>(),
+                           x.data_ptr<float>(), gW.data_ptr<float>(), B, O,
+                           (int)I, S, static_cast<float*>(nullptr));
+      }
+    }
     hipError_t merr = hipGetLastError();
     TORCH_CHECK(merr == hipSuccess, "gw_mfma launch failed: ",
                 hipGetErrorString(merr));
+    return {gW, gb};
+  }
+  if (I > 32) {
+    // 33..64 x rows off the MFMA conditions (ragged or unaligned S, small
+    // O * I, fp64): the generic kernel with a second grid dimension over 32-row
+    // i-slabs, no channel-slice copies
+    const int n_islab = (I + 31) / 32;
+    n_schunk = std::max(1, n_schunk / n_islab);
+    grid = n_schunk * o_tiles;
+#define GW_SLAB(OW_, BIAS_, V)                                                  \
+    hipLaunchKernelGGL((gw_outer_kernel<scalar_t, 32, OW_, BIAS_, V, true>),    \
+                       dim3(grid, n_islab), dim3(kBlock), 0, stream,            \
+                       gz.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),         \
+                       gW.data_ptr<scalar_t>(),                                 \
+                       want_bias ? gb.data_ptr<scalar_t>() : nullptr,           \
+                       B, O, I, S, n_schunk);
+#define GW_SLAB2(OW_)                                                           \
+    if (want_bias) {                                                            \
+      if (vec) { GW_SLAB(OW_, true, true) } else { GW_SLAB(OW_, true, false) }  \
+    } else {                                                                    \
+      if (vec) { GW_SLAB(OW_, false, true) } else { GW_SLAB(OW_, false, false) }\
+    }
+    AT_DISPATCH_FLOATING_TYPES(gz.scalar_type(), "channel_mix_bwd_w", [&] {
+      if (OW == 2) { GW_SLAB2(2) } else { GW_SLAB2(1) }
+    });
+#undef GW_SLAB2
+#undef GW_SLAB
+    hipError_t serr = hipGetLastError();
+    TORCH_CHECK(serr == hipSuccess, "channel_mix_bwd_w launch failed: ",
+                hipGetErrorString(serr));
     return {gW, gb};
   }
   AT_DISPATCH_FLOATING_TYPES(gz.scalar_type(), "channel_mix_bwd_w", [&] {

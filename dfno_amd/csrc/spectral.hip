@@ -274,17 +274,23 @@ __global__ __launch_bounds__(kBlock) void spectral_corners_kernel(
 // eager kernels at the flagship config).  One thread owns (corner, e, o)
 // and streams the I outputs; writes for fixed (i, o) are e-consecutive
 // across lanes (coalesced), as are the x/gy reads.
-template <typename T, int ICAP>
+// ITILE (I_ > ICAP): the i-tile of ICAP channels joins the work index, so a
+// thread's accumulators stay ICAP wide (gy is re-read once per tile).
+template <typename T, int ICAP, bool ITILE = false>
 __global__ __launch_bounds__(kBlock) void spectral_corners_bwd_w_kernel(
     const T* __restrict__ x, const T* __restrict__ gy, MultiGeom<T> mg,
-    int B, int I, int O, long Ftot) {
-  const long total = mg.cum[mg.ncorners] * O;
+    int B, int I_, int O, long Ftot) {
+  const int ntile = ITILE ? (I_ + ICAP - 1) / ICAP : 1;
+  const long total = mg.cum[mg.ncorners] * O * ntile;
   long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
 
   for (long t = t0; t < total; t += stride) {
     long work = t % mg.cum[mg.ncorners];
     int o = (int)(t / mg.cum[mg.ncorners]);
+    int i0 = 0;
+    if (ITILE) { i0 = (o / O) * ICAP; o %= O; }
+    const int I = ITILE ? min(ICAP, I_ - i0) : I_;   // channels of this tile
     int c = 0;
     while (work >= mg.cum[c + 1]) ++c;
     long e = work - mg.cum[c];
@@ -298,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void spectral_corners_bwd_w_kernel(
     for (int b = 0; b < B; ++b) {
       const T* gyb = gy + 2 * (((long)b * O + o) * Ftot + f);
       const T gr = gyb[0], gi = gyb[1];
-      const T* xb = x + 2 * (((long)b * I) * Ftot + f);
+      const T* xb = x + 2 * (((long)b * I_ + i0) * Ftot + f);
 #pragma unroll
       for (int k = 0; k < ICAP; ++k) {
         if (k < I) {
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(kBlock) void spectral_corners_bwd_w_kernel(
 #pragma unroll
     for (int k = 0; k < ICAP; ++k) {
       if (k < I) {
-        long widx = 2 * (((long)k * O + o) * g.nelem + e);
+        long widx = 2 * (((long)(i0 + k) * O + o) * g.nelem + e);
         gw[widx] = accr[k];
         gw[widx + 1] = acci[k];
       }
@@ -625,7 +631,7 @@ void spectral_corners_bwd_w(const at::Tensor& x, const at::Tensor& gy,
   check_c(x, "x"); check_c(gy, "gy");
   TORCH_CHECK(gws.size() == starts.size(), "gws/starts size mismatch");
   int B = (int)x.size(0), I = (int)x.size(1), O = (int)gy.size(1);
-  TORCH_CHECK(I <= 32, "spectral_bwd_w: I must be <= 32");
+  TORCH_CHECK(I <= 64, "spectral_bwd_w: I must be <= 64");
   long Ftot = 1;
   for (int d = 2; d < x.dim(); ++d) Ftot *= x.size(d);
   for (auto& w : gws) {
@@ -634,7 +640,7 @@ void spectral_corners_bwd_w(const at::Tensor& x, const at::Tensor& gy,
   }
   if (B == 0 || gws.empty()) return;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-#define SBW(T, ICAP_)                                                          \
+#define SBW(T, ICAP_, ...)                                                        \
   {                                                                            \
     size_t idx = 0;                                                            \
     while (idx < gws.size()) {                                                 \
@@ -651,8 +657,9 @@ void spectral_corners_bwd_w(const at::Tensor& x, const at::Tensor& gy,
         ++idx;                                                                 \
       }                                                                        \
       if (mg.ncorners == 0) continue;                                          \
-      int grid = launch_grid(mg.cum[mg.ncorners] * O, kBlock, 256L * 16);      \
-      hipLaunchKernelGGL((spectral_corners_bwd_w_kernel<T, ICAP_>),            \
+      int grid = launch_grid(mg.cum[mg.ncorners] * O * ((I + ICAP_ - 1) / ICAP_),\
+                             kBlock, 256L * 16);                               \
+      hipLaunchKernelGGL((spectral_corners_bwd_w_kernel<T, ICAP_ __VA_ARGS__>),\
                          dim3(grid), dim3(kBlock), 0, stream,                  \
                          reinterpret_cast<const T*>(x.data_ptr()),             \
                          reinterpret_cast<const T*>(gy.data_ptr()), mg,        \
@@ -661,10 +668,10 @@ void spectral_corners_bwd_w(const at::Tensor& x, const at::Tensor& gy,
   }
   if (x.scalar_type() == at::kComplexFloat) {
     if (I <= 8) { SBW(float, 8) } else if (I <= 24) { SBW(float, 24) }
-    else { SBW(float, 32) }
+    else if (I <= 32) { SBW(float, 32) } else { SBW(float, 32, , true) }
   } else {
     if (I <= 8) { SBW(double, 8) } else if (I <= 24) { SBW(double, 24) }
-    else { SBW(double, 32) }
+    else if (I <= 32) { SBW(double, 32) } else { SBW(double, 32, , true) }
   }
 #undef SBW
   DFNO_CHECK_LAUNCH("spectral");

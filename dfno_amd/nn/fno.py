@@ -152,7 +152,14 @@ class DistributedFNONd(nn.Module):
             self.dt_comm += r.host_dt
             return proj_head(x, W3, b3, W4, b4)
 
-        if x.is_cuda and x.dtype != torch.bfloat16:
+        # widths 33..64: the composed pair below is native end to end (wide
+        # channel mix for linear3 and its grad-x, the accumulator-resident
+        # 128 -> out kernel for linear4, native grad-W for both), so it is
+        # not a fallback; the note stays for shapes where a torch op runs
+        composed_native = (33 <= l3.in_features <= 64
+                           and l3.out_features == 128
+                           and l4.out_features <= 16)
+        if x.is_cuda and x.dtype != torch.bfloat16 and not composed_native:
             note_fallback("proj_head", f"shape out of fused-kernel range "
                           f"(in={l3.in_features}, mid={l3.out_features}, "
                           f"out={l4.out_features}) or dtype {x.dtype}")

@@ -51,14 +51,42 @@ def _ebf(device):
 
 
 def _bf16_mix_ok(x3: torch.Tensor, I: int, O: int, op: str) -> bool:
-    """bf16-storage channel-mix kernel coverage (csrc/bf16.hip)."""
+    """bf16-storage channel-mix kernel coverage (csrc/bf16.hip); shapes the
+    wide kernel takes instead are not a fallback."""
     if not (x3.is_cuda and x3.dtype == torch.bfloat16):
         return False
     S = x3.shape[2] if x3.dim() == 3 else 0
     ok = S % 8 == 0 and (I <= 32 or O <= 24)
-    if not ok:
+    if not ok and not wide_mix_range(x3.dtype, I, O, S):
         note_fallback(op, f"bf16 shape I={I} O={O} S={S} outside kernel range")
     return ok
+
+
+def wide_mix_range(dtype, I: int, O: int, S: int) -> bool:
+    """Range of the wide channel-mix kernel (csrc/mix_wide.hip) as a pure
+    function of dtype and shape: fp32 or bf16 storage, 33 <= max(I, O) <= 128
+    (either side may be narrower), bf16 rows in whole 16-byte vectors.  The
+    call sites ask it only where the <= 32 kernels do not already apply, so
+    every narrower dispatch stays what it was."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    if min(I, O) < 1 or not 33 <= max(I, O) <= 128:
+        return False
+    return dtype == torch.float32 or S % 8 == 0
+
+
+def _wide_mix_ok(x3: torch.Tensor, I: int, O: int) -> bool:
+    """``wide_mix_range`` for a GPU tensor ``[B, I, S]``."""
+    return bool(x3.is_cuda and x3.dim() == 3
+                and wide_mix_range(x3.dtype, I, O, x3.shape[2]))
+
+
+def _wide_mix(x3, W, b, res, act: bool, wt: bool, need_z: bool):
+    e = torch.empty(0, dtype=x3.dtype, device=x3.device)
+    return _ext.get(required=True).wide_channel_mix(
+        x3.contiguous(), W.contiguous(),
+        b.contiguous() if b is not None else e,
+        res.contiguous() if res is not None else e, act, wt, need_z)
 
 __all__ = ["linear_nd", "add_gelu", "gelu", "linear_res_gelu"]
 
@@ -89,13 +117,18 @@ def _gelu_bwd(gy: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
 
 def _mix_bwd_x(gz: torch.Tensor, W: torch.Tensor, op: str) -> torch.Tensor:
     """gx[b,i,s] = sum_o W[o,i] gz[b,o,s]."""
+    O, I = W.shape
     if gz.is_cuda and _native_dt(gz):
+        if min(I, O) > 32 and _wide_mix_ok(gz, O, I):
+            return _wide_mix(gz, W, None, None, False, True, False)[0]
         return _ext.get(required=True).channel_mix_fwd_t(gz, W)
-    if _bf16_mix_ok(gz, W.shape[0], W.shape[1], op):
+    if _bf16_mix_ok(gz, O, I, op):
         gx, _ = _ext.get(required=True).bf16_channel_mix(
             gz.contiguous(), W.contiguous(), _ebf(gz.device), False, True,
             False, _ebf(gz.device))
         return gx
+    if _wide_mix_ok(gz, O, I):
+        return _wide_mix(gz, W, None, None, False, True, False)[0]
     return torch.einsum("oi,bos->bis", W, gz)
 
 
@@ -103,15 +136,26 @@ def _mix_bwd_w(gz: torch.Tensor, x3: torch.Tensor, W: torch.Tensor,
                want_bias: bool):
     """gW[o,i] = sum_bs gz[b,o,s] x[b,i,s], gb[o] = sum_bs gz[b,o,s]."""
     I, O, S = x3.shape[1], W.shape[0], x3.shape[2]
-    if gz.is_cuda and _native_dt(gz) and I <= 32:
+    bf16 = gz.is_cuda and gz.dtype == torch.bfloat16 and S % 128 == 0
+    if gz.is_cuda and _native_dt(gz) and I <= 64:
         gW, gb = _ext.get(required=True).channel_mix_bwd_w(
             gz.contiguous(), x3.contiguous(), want_bias)
-    elif (gz.is_cuda and gz.dtype == torch.bfloat16 and I <= 32 and O <= 128
-          and S % 128 == 0):
+    elif gz.is_cuda and _native_dt(gz) and O <= 64:
+        # more than 64 x rows against few gz rows (linear4, 128 -> 1): the
+        # same reduction with the roles swapped, gW^T[i,o] = sum x[i] gz[o]
+        gWt, _ = _ext.get(required=True).channel_mix_bwd_w(
+            x3.contiguous(), gz.contiguous(), False)
+        gW = gWt.t().contiguous()
+        gb = gz.sum(dim=(0, 2)) if want_bias else None
+    elif bf16 and I <= 64 and O <= 128:
         gW, gb = _ext.get(required=True).bf16_channel_mix_bwd_w(
             gz.contiguous(), x3.contiguous(), want_bias)
         gW, gb = gW.to(W.dtype), gb.to(W.dtype)
     else:
+        # includes bf16 with more than 64 x rows (linear4 of a composed bf16
+        # head at any width): the pinned bf16 dispatch trace has no grad-W
+        # call there, so that one reduction stays with torch
+
         gW = torch.einsum("bos,bis->oi", gz, x3)
         gb = gz.sum(dim=(0, 2)) if want_bias else None
     return gW, gb if want_bias else None
@@ -152,15 +196,23 @@ class _ChannelMixFn(torch.autograd.Function):
         B, I = x.shape[0], x.shape[1]
         S = x.numel() // max(B * I, 1)
         x3 = x.reshape(B, I, S)
+        O = W.shape[0]
+        # the wide kernel skips the pre-activation store in a no-grad forward
+        need_z = act and any(ctx.needs_input_grad[:3])
         if x.is_cuda and _native_dt(x):
             ext = _ext.get(required=True)
-            y3, z3 = ext.channel_mix_fwd(x3, W, b if b is not None else torch.empty(0, dtype=x.dtype, device=x.device), act)
-        elif _bf16_mix_ok(x3, I, W.shape[0], "channel_mix"):
+            if min(I, O) > 32 and _wide_mix_ok(x3, I, O):
+                y3, z3 = _wide_mix(x3, W, b, None, act, False, need_z)
+            else:
+                y3, z3 = ext.channel_mix_fwd(x3, W, b if b is not None else torch.empty(0, dtype=x.dtype, device=x.device), act)
+        elif _bf16_mix_ok(x3, I, O, "channel_mix"):
             ext = _ext.get(required=True)
             y3, z3 = ext.bf16_channel_mix(
                 x3.contiguous(), W.contiguous(),
                 b.contiguous() if b is not None else _ebf(x.device),
                 act, False, act, _ebf(x.device))
+        elif _wide_mix_ok(x3, I, O):
+            y3, z3 = _wide_mix(x3, W, b, None, act, False, need_z)
         else:
             z3 = torch.einsum("oi,bis->bos", W, x3)
             if b is not None:
@@ -236,7 +288,19 @@ class _LinearResGeluFn(torch.autograd.Function):
         S = x.numel() // max(B * I, 1)
         x3 = x.reshape(B, I, S)
         r3 = res.reshape(B, W.shape[0], S)
-        if x.is_cuda and _native_dt(x):
+        need_z = any(ctx.needs_input_grad)   # wide kernel only: z is optional
+        if x.is_cuda and _native_dt(x) and I > 32:
+            # past the x-resident kernels' 32 input channels
+            if _wide_mix_ok(x3, I, W.shape[0]):
+                y3, z3 = _wide_mix(x3, W, None, r3, True, False, need_z)
+            else:
+                # fp64 (or I > 128): the LDS-path mix, then the fused add+gelu
+                ext = _ext.get(required=True)
+                m3, _ = ext.channel_mix_fwd(
+                    x3.contiguous(), W,
+                    torch.empty(0, dtype=x.dtype, device=x.device), False)
+                y3, z3 = ext.add_gelu_fwd(m3, r3.contiguous())
+        elif x.is_cuda and _native_dt(x):
             ext = _ext.get(required=True)
             y3, z3 = ext.linear_res_gelu_fwd(x3.contiguous(), W, r3.contiguous())
         elif _bf16_mix_ok(x3, x3.shape[1], W.shape[0], "linear_res_gelu"):
@@ -244,6 +308,8 @@ class _LinearResGeluFn(torch.autograd.Function):
             y3, z3 = ext.bf16_channel_mix(x3.contiguous(), W.contiguous(),
                                           _ebf(x.device), True, False, True,
                                           r3.contiguous())
+        elif _wide_mix_ok(x3, I, W.shape[0]):
+            y3, z3 = _wide_mix(x3, W, None, r3, True, False, need_z)
         else:
             z3 = torch.einsum("oi,bis->bos", W, x3) + r3
             y3 = F.gelu(z3)

@@ -157,13 +157,13 @@ class _SpectralConvFn(torch.autograd.Function):
             else:
                 ext.spectral_corners_bwd_x(
                     gy, [w.contiguous() for w in weights], gx, starts)
-            if x.shape[1] <= 32:
+            if x.shape[1] <= 64:
                 gws = [torch.empty_like(w) for w in weights]
                 ext.spectral_corners_bwd_w(x.contiguous(), gy, gws, starts)
             else:
                 from ..dispatch import note_fallback
                 note_fallback("spectral_corners_bwd_w",
-                              f"in_channels {x.shape[1]} > 32 (einsum grad-W)")
+                              f"in_channels {x.shape[1]} > 64 (einsum grad-W)")
                 for w, bounds in zip(weights, bounds_list):
                     sl = _corner_slices(bounds)
                     gws.append(torch.einsum("bo...,bi...->io...",
