@@ -15,9 +15,14 @@
 //    so L1/L2 serve the per-thread scalar loads after the first touch, and
 //    per-line outputs are >= 64B contiguous runs.
 //
-// Twiddles: one table of w^r = exp(-2*pi*i*r/N), r in [0, N), built in LDS
-// at block start (sign applied on read); (j*k) mod N tracked incrementally
-// per kept mode in registers (unrolled + predicated, no scratch).
+// Twiddles: the two generic c2c kernels (dft_c2c_analysis_kernel,
+// dft_c2c_synthesis_kernel) keep w^{jk} of each kept mode in registers and
+// step it by a per-mode recurrence.  Every other kernel reads a host-built
+// [N, modes, 2] table of w^{+-jk} (twiddle_table, cached per process) through
+// lane-uniform scalar loads.
+//
+// Host side: one launch layer (select_le / select_eq, the ladders, launch_tiles)
+// and one decision list per transform; see "Launch layer" below.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -53,11 +58,13 @@ __device__ __forceinline__ void mode_step(int k, int N, double sgn, double* s, d
   sincospi(sgn * (double)(2 * kr) / (double)N, s, c);
 }
 
-// Per-mode twiddle recurrence: each kept mode ki keeps its current factor
-// w^{j k(ki)} in two registers and multiplies by a per-mode step each j —
-// pure independent fma chains that pipeline fully (an LDS table costs a
-// dependent ds_read per MAC and stalls ~10x).  Drift over N <= 64 steps is
-// O(N eps), far below the fp32/fp64 tolerances used here.
+// Per-mode twiddle recurrence of the two generic c2c kernels: each kept mode
+// ki keeps its current factor w^{j k(ki)} in two registers and multiplies by
+// a per-mode step each j, independent fma chains that pipeline fully.  Drift
+// over the N steps of a line is O(N eps).  The paired, radix-8, r2c and c2r
+// kernels do not do this: (j, k) are lane-uniform there, so the host-built
+// table reads compile to scalar loads and the chain updates (4 of every ~5
+// non-MAC VALU ops) go away.
 
 template <typename T>
 __device__ __forceinline__ void cmul_acc(T& cr, T& ci, T sr, T si) {
@@ -180,19 +187,12 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_synthesis_kernel(
 // ---------------------------------------------------------------------------
 // Paired/vectorized C2C variants: when m_hi == m_lo (the FNO case), the
 // suffix mode N-k has twiddle conj(w^{-jk}), so both directions share one
-// recurrence chain per prefix k (plus one for the unpaired k = m_lo); and
+// table entry per prefix k (plus one for the unpaired k = m_lo); and
 // two adjacent `inner` elements are processed per thread (float4 loads,
 // twiddle work amortized): ~1.6x fewer VALU ops per element.
 // ---------------------------------------------------------------------------
 
-// G-way j-split: G threads (same wave) share one pair's j-loop, each
-// walking j = g, g+G, ... with chain step w^{-kG} and start w^{-kg}; the
-// partial sums reduce with log2(G) shfl_xor steps.  Needs G | N so the
-// chains wrap to their start after each line (w^{-kN} = 1).  Raises wave
-// occupancy G-fold for the middle-dim transforms whose outer*pairs alone
-// underfills 1024 SIMDs (the x/y-dim c2c calls of the flagship run at 0.2-
-// 0.5 waves/SIMD otherwise).
-template <typename T, int LCAP, int G = 1>
+template <typename T, int LCAP>
 __global__ __launch_bounds__(kBlock) void dft_c2c_analysis2_kernel(
     const T* __restrict__ in, T* __restrict__ out, const T* __restrict__ tw,
     long outer, int N, long inner, int m_lo, T scale) {
@@ -200,16 +200,11 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_analysis2_kernel(
   // register twiddle chains were 4 of every ~5 non-MAC VALU ops and cost 4
   // LCAP register arrays; (j,k) are lane-uniform so table reads scalarize)
   const int nch = m_lo + 1;
-  constexpr int PL = 64 / G;           // pairs handled per wave per g-group
-  const int lane = (int)(threadIdx.x % 64);
-  const int g = lane / PL;
 
   long pairs = inner / 2;
   long total = outer * pairs;
-  long p0 = (((long)blockIdx.x * blockDim.x + threadIdx.x) / 64) * PL +
-            (lane % PL);
-  long pstride = ((long)gridDim.x * blockDim.x / 64) * PL;
-  const int iters = N / G;             // host guarantees G | N
+  long p0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long pstride = (long)gridDim.x * blockDim.x;
   for (long t = p0; t < total; t += pstride) {
     long o = t / pairs;
     long i = (t % pairs) * 2;
@@ -230,14 +225,13 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_analysis2_kernel(
     // measured 6.3 TB/s for a bare read loop vs 1.9 here without this)
     float4 v;
     if constexpr (std::is_same<T, float>::value)
-      v = *reinterpret_cast<const float4*>(src + 2 * g * inner);
-    for (int sct = 0; sct < iters; ++sct) {
-      const int j = g + sct * G;
+      v = *reinterpret_cast<const float4*>(src);
+    for (int j = 0; j < N; ++j) {
       T x0r, x0i, x1r, x1i;
       if constexpr (std::is_same<T, float>::value) {
         x0r = v.x; x0i = v.y; x1r = v.z; x1i = v.w;
-        if (sct + 1 < iters)
-          v = *reinterpret_cast<const float4*>(src + 2 * (j + G) * inner);
+        if (j + 1 < N)
+          v = *reinterpret_cast<const float4*>(src + 2 * (j + 1) * inner);
       } else {
         x0r = src[2 * j * inner];
         x0i = src[2 * j * inner + 1];
@@ -265,25 +259,6 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_analysis2_kernel(
         }
       }
     }
-    if constexpr (G > 1) {
-      // combine the G partial sums (partners share (o, pair), differ in g)
-#pragma unroll
-      for (int k = 0; k < LCAP; ++k) {
-        if (k < m_lo) {
-          for (int off = PL; off < 64; off <<= 1) {
-            a0r[k] += __shfl_xor(a0r[k], off, 64);
-            a0i[k] += __shfl_xor(a0i[k], off, 64);
-            a1r[k] += __shfl_xor(a1r[k], off, 64);
-            a1i[k] += __shfl_xor(a1i[k], off, 64);
-            b0r[k] += __shfl_xor(b0r[k], off, 64);
-            b0i[k] += __shfl_xor(b0i[k], off, 64);
-            b1r[k] += __shfl_xor(b1r[k], off, 64);
-            b1i[k] += __shfl_xor(b1i[k], off, 64);
-          }
-        }
-      }
-      if (g != 0) continue;            // one g-group writes
-    }
     const int m = 2 * m_lo;
     T* dst = out + 2 * (o * m * inner + i);
 #pragma unroll
@@ -305,26 +280,18 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_analysis2_kernel(
   }
 }
 
-// G-way j-split synthesis: outputs j = g, g+G, ... are independent, so no
-// reduction is needed; each g-group loads the m kept modes (same lines, L1
-// broadcast) and writes its own j's.  Needs G | N for the chain wrap.
-template <typename T, int LCAP, int G = 1>
+template <typename T, int LCAP>
 __global__ __launch_bounds__(kBlock) void dft_c2c_synthesis2_kernel(
     const T* __restrict__ in, T* __restrict__ out, const T* __restrict__ tw,
     long outer, int N, long inner, int m_lo, T scale) {
   // tw is the [N, m_lo+1, 2] table of w^{+jk}; see analysis2 note
   const int nch = m_lo + 1;
-  constexpr int PL = 64 / G;
-  const int lane = (int)(threadIdx.x % 64);
-  const int g = lane / PL;
 
   const int m = 2 * m_lo;
   long pairs = inner / 2;
   long total = outer * pairs;
-  long p0 = (((long)blockIdx.x * blockDim.x + threadIdx.x) / 64) * PL +
-            (lane % PL);
-  long pstride = ((long)gridDim.x * blockDim.x / 64) * PL;
-  const int iters = N / G;             // host guarantees G | N
+  long p0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long pstride = (long)gridDim.x * blockDim.x;
   for (long t = p0; t < total; t += pstride) {
     long o = t / pairs;
     long i = (t % pairs) * 2;
@@ -347,8 +314,7 @@ __global__ __launch_bounds__(kBlock) void dft_c2c_synthesis2_kernel(
       }
     }
     T* dst = out + 2 * (o * N * inner + i);
-    for (int sct = 0; sct < iters; ++sct) {
-      const int j = g + sct * G;
+    for (int j = 0; j < N; ++j) {
       T s0r = T(0), s0i = T(0), s1r = T(0), s1i = T(0);
       auto twj = (const __attribute__((address_space(4))) T*)
           (tw + (long)j * 2 * nch);
@@ -641,16 +607,16 @@ __global__ __launch_bounds__(kBlock) void dft_r2c_glds_kernel(
   // the folded version runs 0.18 ms at the flagship shape (r2cprobe.hip).
   const int N = NT > 0 ? NT : N_;
   const int mm = NT > 0 ? MCAP : m;
-  if constexpr (!std::is_same<T, float>::value) return;  // float-math path
+  static_assert(std::is_same<T, float>::value, "glds r2c is a float-math path");
   constexpr int EPV = 16 / (int)sizeof(TI);          // elements per 16B DMA
   extern __shared__ __align__(16) char smem_raw[];
   TI* ring = reinterpret_cast<TI*>(smem_raw);        // [2][kBlock * N]
   const int tilef = kBlock * N;                      // elements per tile
   // the counted s_waitcnt needs a compile-time-exact per-wave instruction
-  // count: host picks NG = ceil(N/4) rounded up to a supported value and
-  // issues are padded to exactly NG glds (a pad instruction re-stages the
-  // tile's last 1 KiB; it is NOT free, so NG tracks N instead of a single
-  // worst case)
+  // count: the host picks NG (glds_ng: the tile's 16-byte packets per lane,
+  // rounded up to a power of two) and issues are padded to exactly NG glds
+  // (a pad instruction re-stages the tile's last 1 KiB; it is NOT free, so
+  // NG tracks N instead of a single worst case)
   const int wave = (int)(threadIdx.x / 64), lane = (int)(threadIdx.x % 64);
   const long nfl = lines * N;
   long ntiles = (lines + kBlock - 1) / kBlock;
@@ -969,6 +935,213 @@ __global__ __launch_bounds__(LB) void dft_c2r_last_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Launch layer.  The three transforms below are decision lists that read top
+// to bottom; every compile-time parameter of a kernel comes out of one of
+// these selectors, so a kernel is instantiated exactly where it is launched.
+// A new pinned length goes into select_pinned, a new mode cap into with_mcap,
+// a new IO type into the TI / TO parameter of launch_r2c / launch_c2r.
+// ---------------------------------------------------------------------------
+
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// Calls f(int_c<V>) for the first candidate V that v fits (v <= V), or that
+// v equals when EXACT; false when there is none.
+template <bool EXACT, int... Vs, typename F>
+bool select_first(long v, F&& f) {
+  return (((EXACT ? v == Vs : v <= Vs) ? (f(int_c<Vs>{}), true) : false) || ...);
+}
+template <int... Vs, typename F>
+bool select_le(long v, F&& f) { return select_first<false, Vs...>(v, f); }
+template <int... Vs, typename F>
+bool select_eq(long v, F&& f) { return select_first<true, Vs...>(v, f); }
+
+// MCAP, the register cap of the kept-mode arrays (EXACT: m on a cap only)
+template <bool EXACT = false, typename F>
+bool with_mcap(int m, F&& f) { return select_first<EXACT, 8, 16, 24, 32>(m, f); }
+
+// LCAP of the paired c2c kernels: caps the m_lo + 1 twiddle columns
+template <typename F>
+bool with_lcap(int m_lo, F&& f) { return select_le<9, 13, 17>(m_lo + 1, f); }
+
+// LB, lines per tile = block size of the tile kernels: 256 to N = 64, then
+// 128 and 64, which keeps the fp32 [LB, N] LDS tile within 64 KiB (2 blocks/CU)
+template <typename F>
+bool with_tile_lines(int N, F&& f) {
+  return select_le<kMaxN, 2 * kMaxN, 4 * kMaxN>(N, [&](auto ncap) {
+    f(int_c<kBlock * kMaxN / decltype(ncap)::value>{});
+  });
+}
+
+// Pinned (N, m) rows: length and mode count (m == MCAP) are compile-time, so
+// the j-loop unrolls with folded twiddle offsets.  The lengths are listed
+// once, in the order they were tuned; a kernel family has the first PINS.
+template <int PINS, typename F>
+bool select_pinned(int N, int m, F&& f) {
+  auto row = [&](auto rank, auto nt) {
+    if constexpr (decltype(rank)::value < PINS)
+      return N == decltype(nt)::value &&
+             with_mcap<true>(m, [&](auto mc) { f(nt, mc); });
+    else
+      return false;
+  };
+  return row(int_c<0>{}, int_c<30>{}) || row(int_c<1>{}, int_c<64>{}) ||
+         row(int_c<2>{}, int_c<40>{}) || row(int_c<3>{}, int_c<32>{});
+}
+
+// NG of dft_r2c_glds_kernel: 16-byte DMA instructions per wave for one
+// [kBlock, N] tile of elem-byte values (kBlock lanes x 16 bytes per round),
+// rounded up to a power of two
+constexpr int glds_ng(int N, int elem) {
+  const int need = (N * elem + 15) / 16;
+  int ng = 1;
+  while (ng < need) ng *= 2;
+  return ng;
+}
+// the two runtime-N classes of the fp32 ring (N <= 32, N <= 64)
+static_assert(glds_ng(32, 4) == 8 && glds_ng(kMaxN, 4) == 16, "runtime-N NG");
+
+// Launches a tile kernel (r2c / c2r over the last dim): LB threads per block,
+// one block per LB-line tile up to `cap` blocks (the kernels stride over the
+// rest), `bufs` [LB, N] tiles of `elem`-byte values in dynamic LDS.
+template <int LB, typename K, typename TI, typename TO, typename T,
+          typename... Rest>
+void launch_tiles(K kernel, hipStream_t stream, long cap, int bufs, size_t elem,
+                  const TI* in, TO* out, const T* tw, long lines, int N,
+                  Rest... rest) {
+  const long ntiles = (lines + LB - 1) / LB;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(ntiles, cap)), dim3(LB),
+                     bufs * elem * (size_t)LB * N, stream, in, out, tw, lines, N,
+                     rest...);
+}
+
+// r2c rows; T is the math type (table and output), TI the input storage
+// (bf16 as unsigned short, fp32 math):
+//   pinned (N, m)  glds ring, N folded; fp32 math, any TI
+//   runtime N      glds ring; fp32 input only, bf16 IO has no such row
+//   otherwise      tile kernel at the LB of N.  Cap 4096 at LB = 256 for
+//                  fp32/fp64, 2048 for bf16 IO and for N > 64.
+template <typename T, typename TI>
+void launch_r2c(hipStream_t stream, const TI* in, T* out, const T* tw,
+                long lines, int N, int m, T scale, bool factors) {
+  constexpr bool kBf16 = std::is_same_v<TI, unsigned short>;
+  if constexpr (std::is_same_v<T, float>) {
+    // the ring is filled by whole 16-byte packets: aligned base, and at
+    // least one packet in the tensor for the last tile's clamp
+    constexpr int EPV = 16 / (int)sizeof(TI);
+    if (N <= kMaxN && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
+        lines * N >= EPV) {
+      // nt: the pinned length or 0; nmax: the longest N the instantiation
+      // stages, which sets its DMA count
+      auto glds = [&](auto nt, auto nmax, auto mc) {
+        constexpr int NG = glds_ng(decltype(nmax)::value, sizeof(TI));
+        launch_tiles<kBlock>(
+            dft_r2c_glds_kernel<T, decltype(mc)::value, NG, decltype(nt)::value,
+                                TI>,
+            stream, 4096L, /*bufs=*/2, sizeof(TI), in, out, tw, lines, N, m,
+            scale, factors);
+      };
+      if (select_pinned<4>(N, m, [&](auto nt, auto mc) { glds(nt, nt, mc); }))
+        return;
+      if constexpr (!kBf16) {
+        select_le<32, kMaxN>(N, [&](auto nmax) {
+          with_mcap(m, [&](auto mc) { glds(int_c<0>{}, nmax, mc); });
+        });
+        return;
+      }
+    }
+  }
+  with_tile_lines(N, [&](auto lb) {
+    with_mcap(m, [&](auto mc) {
+      constexpr int LB = decltype(lb)::value;
+      launch_tiles<LB>(dft_r2c_last_kernel<T, decltype(mc)::value, LB, TI>,
+                       stream, (LB == kBlock && !kBf16) ? 4096L : 2048L,
+                       /*bufs=*/1, sizeof(T), in, out, tw, lines, N, m, scale,
+                       factors);
+    });
+  });
+}
+
+// c2r rows; T is the math type (table and input), TO the output storage:
+//   pinned (N, m)  fp32 math only: N = 30, 64, 40 for fp32 output, N = 30, 64
+//                  for bf16 output (no N = 40 row was tuned there)
+//   otherwise      the LB of N, cap 4096 at LB = 256, else 2048
+// acc is the optional addend of TO's storage type seen through const T*.
+template <typename T, typename TO>
+void launch_c2r(hipStream_t stream, const T* in, TO* out, const T* tw,
+                long lines, int N, int m, T scale, bool factors, const T* acc) {
+  if constexpr (std::is_same_v<T, float>) {
+    constexpr int PINS = std::is_same_v<TO, unsigned short> ? 2 : 3;
+    if (select_pinned<PINS>(N, m, [&](auto nt, auto mc) {
+          launch_tiles<kBlock>(
+              dft_c2r_last_kernel<T, decltype(mc)::value, decltype(nt)::value,
+                                  kBlock, TO>,
+              stream, 4096L, /*bufs=*/1, sizeof(T), in, out, tw, lines, N, m,
+              scale, factors, acc);
+        }))
+      return;
+  }
+  with_tile_lines(N, [&](auto lb) {
+    with_mcap(m, [&](auto mc) {
+      constexpr int LB = decltype(lb)::value;
+      launch_tiles<LB>(dft_c2r_last_kernel<T, decltype(mc)::value, 0, LB, TO>,
+                       stream, LB == kBlock ? 4096L : 2048L, /*bufs=*/1,
+                       sizeof(T), in, out, tw, lines, N, m, scale, factors, acc);
+    });
+  });
+}
+
+// c2c rows (block 256, no LDS; grid: a thread per line, or per pair of
+// adjacent lines when paired, capped at 4096 blocks):
+//   not paired     generic kernels (register recurrences), MCAP of m
+//   fp32, N = 64 / 128 / 256
+//                  radix-8 x N/8; (64, m_lo = 12), the flagship, folds m_lo too
+//   otherwise      paired kernels, LCAP of m_lo
+// paired: m_hi == m_lo <= 16 and even inner; tw is its [N, m_lo + 1, 2] table.
+template <typename T>
+void launch_c2c(hipStream_t stream, const T* in, T* out, const T* tw,
+                long outer, int n, long inner, int m_lo, int m_hi,
+                bool analysis, bool paired, T scale) {
+  const dim3 grid(launch_grid(outer * (paired ? inner / 2 : inner), kBlock,
+                              256L * 16));
+  if (!paired) {
+    with_mcap(m_lo + m_hi, [&](auto mc) {
+      constexpr int MC = decltype(mc)::value;
+      auto k = analysis ? dft_c2c_analysis_kernel<T, MC>
+                        : dft_c2c_synthesis_kernel<T, MC>;
+      hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, stream, in, out, outer, n,
+                         inner, m_lo, m_hi, scale);
+    });
+    return;
+  }
+  if constexpr (std::is_same_v<T, float>) {
+    auto radix = [&](auto lc, auto mlt, auto nbt) {
+      constexpr int LC = decltype(lc)::value, MLT = decltype(mlt)::value,
+                    NBT = decltype(nbt)::value;
+      auto k = analysis ? dft_c2c_radix8_ana_kernel<T, LC, MLT, NBT>
+                        : dft_c2c_radix8_syn_kernel<T, LC, MLT, NBT>;
+      hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, stream, in, out, tw, outer,
+                         inner, m_lo, scale);
+    };
+    if (n == 64 && m_lo == 12) {
+      radix(int_c<13>{}, int_c<12>{}, int_c<8>{});
+      return;
+    }
+    if (select_eq<64, 128, 256>(n, [&](auto nn) {
+          with_lcap(m_lo, [&](auto lc) {
+            radix(lc, int_c<0>{}, int_c<decltype(nn)::value / 8>{});
+          });
+        }))
+      return;
+  }
+  with_lcap(m_lo, [&](auto lc) {
+    constexpr int LC = decltype(lc)::value;
+    auto k = analysis ? dft_c2c_analysis2_kernel<T, LC>
+                      : dft_c2c_synthesis2_kernel<T, LC>;
+    hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, stream, in, out, tw, outer, n,
+                       inner, m_lo, scale);
+  });
+}
 
 void split_dims(const at::Tensor& x, int dim, long& outer, long& inner) {
   outer = 1;
@@ -976,13 +1149,6 @@ void split_dims(const at::Tensor& x, int dim, long& outer, long& inner) {
   inner = 1;
   for (int d = dim + 1; d < x.dim(); ++d) inner *= x.size(d);
 }
-
-#define DFT_MDISPATCH(KERNEL, ...)                                             \
-  if (m <= 8) { hipLaunchKernelGGL((KERNEL<scalar_t, 8>), __VA_ARGS__); }      \
-  else if (m <= 16) { hipLaunchKernelGGL((KERNEL<scalar_t, 16>), __VA_ARGS__); } \
-  else if (m <= 24) { hipLaunchKernelGGL((KERNEL<scalar_t, 24>), __VA_ARGS__); } \
-  else { TORCH_CHECK(m <= 32, "dft: m > 32 unsupported natively");             \
-         hipLaunchKernelGGL((KERNEL<scalar_t, 32>), __VA_ARGS__); }
 
 // Cached [N, m, 2] twiddle table (fp64 sincos on host, cast to T): one per
 // (N, m, direction, dtype) per process; ranks own one device each.
@@ -1019,7 +1185,7 @@ at::Tensor dft_c2c(const at::Tensor& x, int64_t dim, int64_t n,
               "dft_c2c: complex input");
   TORCH_CHECK(n <= kMaxNBig, "dft_c2c: N too large");
   const int m = (int)(m_lo + m_hi);
-  TORCH_CHECK(m <= 64 && m <= n, "dft_c2c: bad mode count");
+  TORCH_CHECK(m <= 32 && m <= n, "dft_c2c: bad mode count (m <= 32, m <= N)");
   TORCH_CHECK(x.size(dim) == (analysis ? n : m), "dft_c2c: dim extent mismatch");
 
   long outer, inner;
@@ -1030,106 +1196,17 @@ at::Tensor dft_c2c(const at::Tensor& x, int64_t dim, int64_t n,
   if (x.numel() == 0) return out;
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = launch_grid(outer * inner, kBlock, 256L * 16);
-
-  bool paired = (m_hi == m_lo) && (inner % 2 == 0) && m_lo <= 16;
-  static const bool no_radix = []() {
-    const char* e = getenv("DFNO_DFT_NO_RADIX");  // A/B knob
-    return e && e[0] == '1';
-  }();
-  // j-split degree: raise wave occupancy when outer*pairs alone underfills
-  // the 1024 SIMDs (x/y-dim transforms); G must divide n for the chain wrap
-  int Gsel = 1;
-  if (paired) {
-    static const long gtarget = []() {
-      const char* e = getenv("DFNO_DFT_GTARGET");  // threads wanted (tunable)
-      // default 1 = j-split off: measured on MI355X, G>1 LOSES at every
-      // flagship shape (y-dim c2c 0.119 -> 0.137 ms at G=4) -- the per-wave
-      // load stream already saturates at 0.5 waves/SIMD and narrowing the
-      // contiguous chunk from 1 KB to 256 B costs more than the extra
-      // occupancy buys.  Kept as a knob for other shapes.
-      return e ? atol(e) : 1L;
-    }();
-    long pwork = outer * (inner / 2);
-    while (Gsel < 8 && (n % (Gsel * 2) == 0) && pwork * Gsel < gtarget)
-      Gsel *= 2;
-  }
-  int grid2 = paired ? launch_grid(outer * (inner / 2) * Gsel, kBlock, 256L * 16)
-                     : grid;
-#define DFT_LG(KERNEL, LC, ...)                                                \
-  switch (Gsel) {                                                              \
-    case 8: hipLaunchKernelGGL((KERNEL<scalar_t, LC, 8>), __VA_ARGS__); break; \
-    case 4: hipLaunchKernelGGL((KERNEL<scalar_t, LC, 4>), __VA_ARGS__); break; \
-    case 2: hipLaunchKernelGGL((KERNEL<scalar_t, LC, 2>), __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL((KERNEL<scalar_t, LC, 1>), __VA_ARGS__);       \
-  }
-#define DFT_LDISPATCH(KERNEL, ...)                                             \
-  if (m_lo <= 8) { DFT_LG(KERNEL, 9, __VA_ARGS__) }                            \
-  else if (m_lo <= 12) { DFT_LG(KERNEL, 13, __VA_ARGS__) }                     \
-  else { DFT_LG(KERNEL, 17, __VA_ARGS__) }
+  const auto real = c10::toRealValueType(x.scalar_type());
+  const bool paired = (m_hi == m_lo) && (inner % 2 == 0) && m_lo <= 16;
   at::Tensor tw;
   if (paired)
-    tw = twiddle_table((int)n, (int)m_lo + 1, analysis,
-                       x.options().dtype(c10::toRealValueType(x.scalar_type())));
-  // radix-8xNB eligibility: N in {64, 128, 256} (NBT 8/16/32), fp32, paired
-  bool radix_ok = paired && (n == 64 || n == 128 || n == 256) &&
-                  c10::toRealValueType(x.scalar_type()) == at::kFloat &&
-                  !no_radix;
-#define DFT_RADIX_LC(KERNEL, NBT)                                              \
-  if (n == 64 && m_lo == 12) { /* flagship: fully folded */                    \
-    hipLaunchKernelGGL((KERNEL<scalar_t, 13, 12, 8>), dim3(grid2),             \
-                       dim3(kBlock), 0, stream, inp, op,                       \
-                       tw.data_ptr<scalar_t>(), outer, inner, (int)m_lo,       \
-                       (scalar_t)scale);                                       \
-  } else if (m_lo <= 8) {                                                      \
-    hipLaunchKernelGGL((KERNEL<scalar_t, 9, 0, NBT>), dim3(grid2),             \
-                       dim3(kBlock), 0, stream, inp, op,                       \
-                       tw.data_ptr<scalar_t>(), outer, inner, (int)m_lo,       \
-                       (scalar_t)scale);                                       \
-  } else if (m_lo <= 12) {                                                     \
-    hipLaunchKernelGGL((KERNEL<scalar_t, 13, 0, NBT>), dim3(grid2),            \
-                       dim3(kBlock), 0, stream, inp, op,                       \
-                       tw.data_ptr<scalar_t>(), outer, inner, (int)m_lo,       \
-                       (scalar_t)scale);                                       \
-  } else {                                                                     \
-    hipLaunchKernelGGL((KERNEL<scalar_t, 17, 0, NBT>), dim3(grid2),            \
-                       dim3(kBlock), 0, stream, inp, op,                       \
-                       tw.data_ptr<scalar_t>(), outer, inner, (int)m_lo,       \
-                       (scalar_t)scale);                                       \
-  }
-#define DFT_RADIX(KERNEL)                                                      \
-  if (n == 256) { DFT_RADIX_LC(KERNEL, 32) }                                   \
-  else if (n == 128) { DFT_RADIX_LC(KERNEL, 16) }                              \
-  else { DFT_RADIX_LC(KERNEL, 8) }
-  AT_DISPATCH_FLOATING_TYPES(c10::toRealValueType(x.scalar_type()), "dft_c2c", [&] {
-    auto inp = reinterpret_cast<const scalar_t*>(x.data_ptr());
-    auto op = reinterpret_cast<scalar_t*>(out.data_ptr());
-    if (radix_ok && analysis) {
-      DFT_RADIX(dft_c2c_radix8_ana_kernel)
-    } else if (paired && analysis) {
-      DFT_LDISPATCH(dft_c2c_analysis2_kernel, dim3(grid2), dim3(kBlock), 0,
-                    stream, inp, op, tw.data_ptr<scalar_t>(), outer, (int)n,
-                    inner, (int)m_lo, (scalar_t)scale)
-    } else if (radix_ok && !analysis) {
-      DFT_RADIX(dft_c2c_radix8_syn_kernel)
-    } else if (paired) {
-      DFT_LDISPATCH(dft_c2c_synthesis2_kernel, dim3(grid2), dim3(kBlock), 0,
-                    stream, inp, op, tw.data_ptr<scalar_t>(), outer, (int)n,
-                    inner, (int)m_lo, (scalar_t)scale)
-    } else if (analysis) {
-      DFT_MDISPATCH(dft_c2c_analysis_kernel, dim3(grid), dim3(kBlock), 0, stream,
-                    inp, op, outer, (int)n, inner, (int)m_lo, (int)m_hi,
-                    (scalar_t)scale)
-    } else {
-      DFT_MDISPATCH(dft_c2c_synthesis_kernel, dim3(grid), dim3(kBlock), 0, stream,
-                    inp, op, outer, (int)n, inner, (int)m_lo, (int)m_hi,
-                    (scalar_t)scale)
-    }
+    tw = twiddle_table((int)n, (int)m_lo + 1, analysis, x.options().dtype(real));
+  AT_DISPATCH_FLOATING_TYPES(real, "dft_c2c", [&] {
+    launch_c2c(stream, reinterpret_cast<const scalar_t*>(x.data_ptr()),
+               reinterpret_cast<scalar_t*>(out.data_ptr()),
+               paired ? tw.data_ptr<scalar_t>() : nullptr, outer, (int)n, inner,
+               (int)m_lo, (int)m_hi, analysis, paired, (scalar_t)scale);
   });
-#undef DFT_RADIX
-#undef DFT_RADIX_LC
-#undef DFT_LDISPATCH
-#undef DFT_LG
   DFNO_CHECK_LAUNCH("dft_c2c");
   return out;
 }
@@ -1143,6 +1220,9 @@ static at::Tensor dft_r2c_impl(const at::Tensor& x, int64_t dim, int64_t m,
   TORCH_CHECK(m <= 32, "dft_r2c: m > 32 unsupported natively");
   long lines = x.numel() / std::max(N, 1);
 
+  // bf16 input: staged raw (glds) or converted at the LDS write, fp32
+  // compute, complex64 out; the bf16 model's real-side transforms read half
+  // the bytes and skip the boundary-cast pass entirely
   const bool bf16_in = x.scalar_type() == at::kBFloat16;
   auto sizes = x.sizes().vec();
   sizes[dim] = m;
@@ -1151,114 +1231,21 @@ static at::Tensor dft_r2c_impl(const at::Tensor& x, int64_t dim, int64_t m,
   if (x.numel() == 0) return out;
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  long ntiles = (lines + kBlock - 1) / kBlock;
-  int grid = (int)std::min(ntiles, 4096L);
   auto tw = twiddle_table(N, (int)m, /*analysis=*/true,
                           x.options().dtype(bf16_in ? at::kFloat
                                                     : x.scalar_type()));
   if (bf16_in) {
-    // bf16-IO variant: bf16 staged + converted at the LDS write, fp32
-    // compute, complex64 out — the bf16 model's real-side transforms read
-    // half the bytes and skip the boundary-cast pass entirely
-    auto inp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-    auto op = reinterpret_cast<float*>(out.data_ptr());
-    bool glds_ok = N <= 64 &&
-                   ((reinterpret_cast<uintptr_t>(inp) & 15) == 0) &&
-                   ((long)kBlock * N) % 8 == 0 && lines * N >= 8;
-    bool mexact = (m == 8 || m == 16 || m == 24 || m == 32);
-    if (glds_ok && mexact && (N == 30 || N == 64 || N == 40 || N == 32)) {
-      // DMA the raw bf16 tile (glds ring at half the fp32 footprint)
-      size_t smem2 = 2 * sizeof(unsigned short) * (size_t)kBlock * N;
-#define R2CGB(MC, NGV, NTV)                                                    \
-      hipLaunchKernelGGL((dft_r2c_glds_kernel<float, MC, NGV, NTV,             \
-                                              unsigned short>),                \
-                         dim3(grid), dim3(kBlock), smem2, stream, inp, op,     \
-                         tw.data_ptr<float>(), lines, N, (int)m,               \
-                         (float)scale, factors);
-#define R2CGB_M(NGV, NTV)                                                      \
-      if (m == 8) { R2CGB(8, NGV, NTV) } else if (m == 16) { R2CGB(16, NGV, NTV) } \
-      else if (m == 24) { R2CGB(24, NGV, NTV) } else { R2CGB(32, NGV, NTV) }
-      if (N == 30) { R2CGB_M(4, 30) }
-      else if (N == 64) { R2CGB_M(8, 64) }
-      else if (N == 40) { R2CGB_M(8, 40) }
-      else { R2CGB_M(4, 32) }
-#undef R2CGB_M
-#undef R2CGB
-      DFNO_CHECK_LAUNCH("dft_r2c_bf16");
-      return out;
-    }
-#define R2C_BF(MC, LBV)                                                        \
-    { long nt2 = (lines + LBV - 1) / LBV;                                      \
-      int grid2 = (int)std::min(nt2, 2048L);                                   \
-      size_t smem2 = sizeof(float) * (size_t)LBV * N;                          \
-      hipLaunchKernelGGL((dft_r2c_last_kernel<float, MC, LBV, unsigned short>),\
-                         dim3(grid2), dim3(LBV), smem2, stream, inp, op,       \
-                         tw.data_ptr<float>(), lines, N, (int)m,               \
-                         (float)scale, factors); }
-#define R2C_BF_M(LBV)                                                          \
-    if (m <= 8) { R2C_BF(8, LBV) } else if (m <= 16) { R2C_BF(16, LBV) }       \
-    else if (m <= 24) { R2C_BF(24, LBV) } else { R2C_BF(32, LBV) }
-    if (N <= 64) { R2C_BF_M(256) }
-    else if (N <= 128) { R2C_BF_M(128) }
-    else { R2C_BF_M(64) }
-#undef R2C_BF_M
-#undef R2C_BF
-    DFNO_CHECK_LAUNCH("dft_r2c_bf16");
-    return out;
+    launch_r2c(stream, usp(x), reinterpret_cast<float*>(out.data_ptr()),
+               tw.data_ptr<float>(), lines, N, (int)m, (float)scale, factors);
+  } else {
+    AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "dft_r2c", [&] {
+      launch_r2c(stream, x.data_ptr<scalar_t>(),
+                 reinterpret_cast<scalar_t*>(out.data_ptr()),
+                 tw.data_ptr<scalar_t>(), lines, N, (int)m, (scalar_t)scale,
+                 factors);
+    });
   }
-#define R2CG(MC, NGV, NTV)                                                     \
-      hipLaunchKernelGGL((dft_r2c_glds_kernel<scalar_t, MC, NGV, NTV>),        \
-                         dim3(grid), dim3(kBlock), smem2, stream, inp, op,     \
-                         tw.data_ptr<scalar_t>(), lines, N, (int)m,            \
-                         (scalar_t)scale, factors);
-#define R2CG_M(NGV, NTV)                                                       \
-      if (m <= 8) { R2CG(8, NGV, NTV) } else if (m <= 16) { R2CG(16, NGV, NTV) } \
-      else if (m <= 24) { R2CG(24, NGV, NTV) } else { R2CG(32, NGV, NTV) }
-#define R2C_BIG(MC, LBV)                                                       \
-      { long nt2 = (lines + LBV - 1) / LBV;                                    \
-        int grid2 = (int)std::min(nt2, 2048L);                                 \
-        size_t smem2 = sizeof(scalar_t) * (size_t)LBV * N;                     \
-        hipLaunchKernelGGL((dft_r2c_last_kernel<scalar_t, MC, LBV>),           \
-                           dim3(grid2), dim3(LBV), smem2, stream, inp, op,     \
-                           tw.data_ptr<scalar_t>(), lines, N, (int)m,          \
-                           (scalar_t)scale, factors); }
-#define R2C_BIG_M(LBV)                                                         \
-      if (m <= 8) { R2C_BIG(8, LBV) } else if (m <= 16) { R2C_BIG(16, LBV) }   \
-      else if (m <= 24) { R2C_BIG(24, LBV) } else { R2C_BIG(32, LBV) }
-  AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "dft_r2c", [&] {
-    size_t smem = sizeof(scalar_t) * (size_t)kBlock * N;
-    auto inp = x.data_ptr<scalar_t>();
-    auto op = reinterpret_cast<scalar_t*>(out.data_ptr());
-    if (N > kMaxN) {
-      // big-N path: smaller lines-per-tile keeps the LDS tile <= 64 KiB
-      // (2 blocks/CU); one thread per line, table-driven naive DFT
-      if (N <= 128) { R2C_BIG_M(128) } else { R2C_BIG_M(64) }
-      return;
-    }
-    bool glds_ok = std::is_same<scalar_t, float>::value &&
-                   ((reinterpret_cast<uintptr_t>(inp) & 15) == 0) &&
-                   ((long)kBlock * N) % 4 == 0 && lines * N >= 4;
-    if (glds_ok) {
-      size_t smem2 = 2 * smem;   // double-buffered ring
-      // common N with m on an MCAP boundary get the fully-folded fast path
-      bool mexact = (m == 8 || m == 16 || m == 24 || m == 32);
-      if (mexact && N == 30) { R2CG_M(8, 30) }
-      else if (mexact && N == 64) { R2CG_M(16, 64) }
-      else if (mexact && N == 40) { R2CG_M(16, 40) }
-      else if (mexact && N == 32) { R2CG_M(8, 32) }
-      else if (N <= 32) { R2CG_M(8, 0) }   // ceil(N/4) <= 8 glds per wave
-      else { R2CG_M(16, 0) }
-    } else {
-      DFT_MDISPATCH(dft_r2c_last_kernel, dim3(grid), dim3(kBlock), smem,
-                    stream, inp, op, tw.data_ptr<scalar_t>(), lines, N,
-                    (int)m, (scalar_t)scale, factors)
-    }
-  });
-#undef R2C_BIG_M
-#undef R2C_BIG
-#undef R2CG_M
-#undef R2CG
-  DFNO_CHECK_LAUNCH("dft_r2c");
+  DFNO_CHECK_LAUNCH(bf16_in ? "dft_r2c_bf16" : "dft_r2c");
   return out;
 }
 
@@ -1278,111 +1265,47 @@ static at::Tensor dft_c2r_impl(const at::Tensor& y, int64_t dim, int64_t n_out,
 
   auto sizes = y.sizes().vec();
   sizes[dim] = N;
-  if (out_bf16) {
-    TORCH_CHECK(y.scalar_type() == at::kComplexFloat,
-                "dft_c2r: bf16 output needs c64 input");
-    TORCH_CHECK(!accum.defined() || accum.numel() == 0 ||
-                (accum.scalar_type() == at::kBFloat16 &&
-                 accum.is_contiguous()),
-                "dft_c2r: bf16 accumulate must be contiguous bf16");
-  }
+  TORCH_CHECK(!out_bf16 || y.scalar_type() == at::kComplexFloat,
+              "dft_c2r: bf16 output needs c64 input");
   auto out = at::empty(sizes, y.options().dtype(
       out_bf16 ? at::kBFloat16
                : (y.scalar_type() == at::kComplexFloat ? at::kFloat
                                                        : at::kDouble)));
+  // the optional addend (an empty tensor means none) has the output's dtype
+  // and size
+  const bool has_acc = accum.defined() && accum.numel() > 0;
+  TORCH_CHECK(!out_bf16 || !has_acc || (accum.scalar_type() == at::kBFloat16 &&
+                                        accum.is_contiguous()),
+              "dft_c2r: bf16 accumulate must be contiguous bf16");
   if (y.numel() == 0) return out;
-
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  long ntiles = (lines + kBlock - 1) / kBlock;
-  int grid = (int)std::min(ntiles, 4096L);
-  auto tw = twiddle_table(N, m, /*analysis=*/false,
-                          out.options().dtype(out_bf16 ? at::kFloat
-                                                       : out.scalar_type()));
-  if (out_bf16) {
-    // bf16-output writeback (fp32 compute/LDS tile), flagship NT folding kept
-    auto inp = reinterpret_cast<const float*>(y.data_ptr());
-    auto op = reinterpret_cast<unsigned short*>(out.data_ptr());
-    const float* accb = nullptr;               // packed bf16 through T*
-    if (accum.defined() && accum.numel() > 0) {
-      TORCH_CHECK(accum.numel() == out.numel(), "dft_c2r: accumulate shape");
-      accb = reinterpret_cast<const float*>(accum.data_ptr());
-    }
-#define C2RB(MC, NTV, LBV)                                                     \
-    { long nt2 = (lines + LBV - 1) / LBV;                                      \
-      int grid2 = (int)std::min(nt2, LBV == kBlock ? 4096L : 2048L);           \
-      size_t smem2 = sizeof(float) * (size_t)LBV * N;                          \
-      hipLaunchKernelGGL(                                                      \
-          (dft_c2r_last_kernel<float, MC, NTV, LBV, unsigned short>),          \
-          dim3(grid2), dim3(LBV), smem2, stream, inp, op,                      \
-          tw.data_ptr<float>(), lines, N, (int)m, (float)scale, factors,       \
-          accb); }
-#define C2RB_M(NTV, LBV)                                                       \
-    if (m <= 8) { C2RB(8, NTV, LBV) } else if (m <= 16) { C2RB(16, NTV, LBV) } \
-    else if (m <= 24) { C2RB(24, NTV, LBV) } else { C2RB(32, NTV, LBV) }
-    const bool mexact = (m == 8 || m == 16 || m == 24 || m == 32);
-    if (mexact && N == 30) { C2RB_M(30, kBlock) }
-    else if (mexact && N == 64) { C2RB_M(64, kBlock) }
-    else if (N <= 64) { C2RB_M(0, kBlock) }
-    else if (N <= 128) { C2RB_M(0, 128) }
-    else { C2RB_M(0, 64) }
-#undef C2RB_M
-#undef C2RB
-    DFNO_CHECK_LAUNCH("dft_c2r_bf16");
-    return out;
-  }
-#define C2RG(MC, NTV)                                                          \
-      hipLaunchKernelGGL((dft_c2r_last_kernel<scalar_t, MC, NTV>),             \
-                         dim3(grid), dim3(kBlock), smem, stream, inp, op,      \
-                         tw.data_ptr<scalar_t>(), lines, N, (int)m,            \
-                         (scalar_t)scale, factors, accp);
-#define C2R_BIG(MC, LBV)                                                       \
-      { long nt2 = (lines + LBV - 1) / LBV;                                    \
-        int grid2 = (int)std::min(nt2, 2048L);                                 \
-        size_t smem2 = sizeof(scalar_t) * (size_t)LBV * N;                     \
-        hipLaunchKernelGGL((dft_c2r_last_kernel<scalar_t, MC, 0, LBV>),        \
-                           dim3(grid2), dim3(LBV), smem2, stream, inp, op,     \
-                           tw.data_ptr<scalar_t>(), lines, N, (int)m,          \
-                           (scalar_t)scale, factors, accp); }
-#define C2R_BIG_M(LBV)                                                         \
-      if (m <= 8) { C2R_BIG(8, LBV) } else if (m <= 16) { C2R_BIG(16, LBV) }   \
-      else if (m <= 24) { C2R_BIG(24, LBV) } else { C2R_BIG(32, LBV) }
-  if (accum.defined() && accum.numel() > 0) {
+  if (has_acc && out_bf16) {
+    TORCH_CHECK(accum.numel() == out.numel(), "dft_c2r: accumulate shape");
+  } else if (has_acc) {
     TORCH_CHECK(accum.is_cuda() && accum.is_contiguous() &&
                 accum.numel() == out.numel() &&
                 accum.scalar_type() == out.scalar_type(),
                 "dft_c2r: bad accumulate tensor");
   }
-  AT_DISPATCH_FLOATING_TYPES(out.scalar_type(), "dft_c2r", [&] {
-    size_t smem = sizeof(scalar_t) * (size_t)kBlock * N;
-    auto inp = reinterpret_cast<const scalar_t*>(y.data_ptr());
-    auto op = out.data_ptr<scalar_t>();
-    const scalar_t* accp = (accum.defined() && accum.numel() > 0)
-                               ? accum.data_ptr<scalar_t>() : nullptr;
-    if (N > kMaxN) {
-      if (N <= 128) { C2R_BIG_M(128) } else { C2R_BIG_M(64) }
-      return;
-    }
-    bool mexact = std::is_same<scalar_t, float>::value &&
-                  (m == 8 || m == 16 || m == 24 || m == 32);
-    if (mexact && N == 30) {
-      if (m == 8) { C2RG(8, 30) } else if (m == 16) { C2RG(16, 30) }
-      else if (m == 24) { C2RG(24, 30) } else { C2RG(32, 30) }
-    } else if (mexact && N == 64) {
-      if (m == 8) { C2RG(8, 64) } else if (m == 16) { C2RG(16, 64) }
-      else if (m == 24) { C2RG(24, 64) } else { C2RG(32, 64) }
-    } else if (mexact && N == 40) {
-      if (m == 8) { C2RG(8, 40) } else if (m == 16) { C2RG(16, 40) }
-      else if (m == 24) { C2RG(24, 40) } else { C2RG(32, 40) }
-    } else {
-      DFT_MDISPATCH(dft_c2r_last_kernel, dim3(grid), dim3(kBlock), smem,
-                    stream, inp, op, tw.data_ptr<scalar_t>(), lines, N,
-                    (int)m, (scalar_t)scale, factors, accp)
-    }
-  });
-#undef C2R_BIG_M
-#undef C2R_BIG
-#undef C2RG
-  DFNO_CHECK_LAUNCH("dft_c2r");
+  const void* accp = has_acc ? accum.data_ptr() : nullptr;
+
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  auto tw = twiddle_table(N, m, /*analysis=*/false,
+                          out.options().dtype(out_bf16 ? at::kFloat
+                                                       : out.scalar_type()));
+  if (out_bf16) {
+    // bf16-output writeback (fp32 compute and LDS tile); the kernel reads the
+    // packed-bf16 addend through its fp32-typed parameter
+    launch_c2r(stream, reinterpret_cast<const float*>(y.data_ptr()),
+               usp_mut(out), tw.data_ptr<float>(), lines, N, m, (float)scale,
+               factors, static_cast<const float*>(accp));
+  } else {
+    AT_DISPATCH_FLOATING_TYPES(out.scalar_type(), "dft_c2r", [&] {
+      launch_c2r(stream, reinterpret_cast<const scalar_t*>(y.data_ptr()),
+                 out.data_ptr<scalar_t>(), tw.data_ptr<scalar_t>(), lines, N, m,
+                 (scalar_t)scale, factors, static_cast<const scalar_t*>(accp));
+    });
+  }
+  DFNO_CHECK_LAUNCH(out_bf16 ? "dft_c2r_bf16" : "dft_c2r");
   return out;
 }
 

@@ -24,7 +24,8 @@ and ``zt_fwd(stash_key=)`` return an ordering token next to the spectrum, and
 their adjoints add what the block epilogue left under the key; the second
 consumer is wired up by ``ops.epilogue.block_epilogue`` alone, which is the
 only caller of ``StashGradFn``.  And the fused (z,t) plane transforms of
-csrc/dft2d.hip, whose caps are stated once, in ``zt_caps_ok``.
+csrc/dft2d.hip, whose caps are stated once, in ``zt_caps_ok``, as those of
+the 1-D kernels of csrc/dft.hip are in ``dft_caps_ok``.
 """
 
 from __future__ import annotations
@@ -43,16 +44,24 @@ __all__ = ["rfft_trunc", "fft_trunc", "pad_ifft", "pad_irfft"]
 # 256^3 weak-scaling grids and nt <= 256 temporal scaling natively
 # (VERDICT.md round-1 item 2).
 _MAX_N = 256
+_MAX_M = 32
+
+
+def dft_caps_ok(n: int, m: int) -> bool:
+    """The caps of csrc/dft.hip, stated once: transform length and kept-mode
+    count of the 1-D kernels.  Every policy that must know whether they own
+    a 1-D transform tests this."""
+    return n <= _MAX_N and m <= _MAX_M
 
 
 def _native_ok(x: torch.Tensor, n: int, m: int, op: str) -> bool:
     if not x.is_cuda:
         return False
-    ok = (n <= _MAX_N and m <= 32
+    ok = (dft_caps_ok(n, m)
           and x.dtype in (torch.float32, torch.complex64,
                           torch.float64, torch.complex128))
     if not ok:
-        note_fallback(op, f"N={n} (cap {_MAX_N}) / m={m} (cap 32) / "
+        note_fallback(op, f"N={n} (cap {_MAX_N}) / m={m} (cap {_MAX_M}) / "
                       f"dtype {x.dtype} outside the native-DFT range")
     return ok
 
@@ -269,7 +278,7 @@ def stash_fusable(x, dim, m) -> bool:
     m = min(m, x.shape[d] // 2 + 1)
     if not (d == x.dim() - 1 and x.is_cuda and x.numel() > 0
             and torch.is_grad_enabled() and x.requires_grad
-            and x.shape[d] <= _MAX_N and m <= 32):
+            and dft_caps_ok(x.shape[d], m)):
         return False
     if x.dtype == torch.bfloat16:
         # bf16 stash: bf16-IO r2c forward + bf16 adjoint with the packed
@@ -396,7 +405,7 @@ def rfft_bf16_native_ok(x, dim, m) -> bool:
     d = dim % x.dim()
     m = min(m, x.shape[d] // 2 + 1)
     return (d == x.dim() - 1 and x.is_cuda and x.dtype == torch.bfloat16
-            and x.shape[d] <= _MAX_N and m <= 32)
+            and dft_caps_ok(x.shape[d], m))
 
 
 def rfft_trunc(x, dim, m):

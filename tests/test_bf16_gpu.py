@@ -175,6 +175,13 @@ def test_bf16_gelu_and_add_gelu():
 @pytest.mark.parametrize("shape,m", [
     ((1, 4, 9, 9, 30), 8),     # flagship t-dim
     ((2, 3, 6, 64), 12),
+    # launch rows at 2 * 256 + 37 lines (two full tiles and a ragged tail)
+    ((549, 40), 8),            # r2c pinned (40, 8); c2r N = 40 has no pinned row
+    ((549, 32), 16),           # r2c pinned (32, 16)
+    ((549, 20), 5),            # unpinned N: converting tile kernels
+    ((549, 64), 16),           # r2c and c2r pinned (64, 16)
+    ((549, 128), 16),          # N > 64: 128-line tiles
+    ((549, 256), 32),          # N > 128: 64-line tiles
 ])
 def test_bf16_io_rfft_and_irfft(shape, m):
     """bf16-IO transform kernels: bf16 in -> c64 spectrum -> bf16 out,

@@ -326,10 +326,18 @@ def test_proj_head(dtype, tt, B, I, M, O2, S):
 # fused truncated-spectrum DFTs vs torch.fft compositions
 # ---------------------------------------------------------------------------
 
+_ROW_LINES = 2 * 256 + 37
+
+
 @pytest.mark.parametrize("dtype,tt", [(torch.float32, 2e-4), (torch.float64, 1e-11)])
 @pytest.mark.parametrize("shape,dim,N,m", [
     ((1, 20, 9, 9, 6, 30), 5, 30, 8),    # flagship t-dim rfft
     ((2, 4, 7, 15), 3, 15, 5),           # odd N
+    # launch rows at 2 * 256 + 37 lines (two full tiles and a ragged tail);
+    # the backward is the c2r adjoint of the same (N, m)
+    ((_ROW_LINES, 64), 1, 64, 16),       # fp32: pinned (64, 16) r2c and c2r
+    ((_ROW_LINES, 48), 1, 48, 12),       # fp32: runtime-N ring, N <= 64 class
+    ((_ROW_LINES, 20), 1, 20, 5),        # fp32: runtime-N ring, N <= 32 class
 ])
 def test_dft_rfft_trunc(dtype, tt, shape, dim, N, m):
     from dfno_amd.ops.fft import rfft_trunc, _t_rfft_trunc
@@ -344,6 +352,47 @@ def test_dft_rfft_trunc(dtype, tt, shape, dim, N, m):
     yr.backward(g)
     assert torch.allclose(x.grad, xr.grad, rtol=tt, atol=tt * 10), \
         f"bwd {(x.grad-xr.grad).abs().max()}"
+
+
+@pytest.mark.parametrize("N,m,misaligned", [
+    (40, 24, False),                     # pinned (40, 24)
+    (32, 32, False),                     # pinned (32, 32)
+    (30, 8, True),                       # unaligned base: tile kernel, not the ring
+])
+def test_dft_rfft_trunc_rows_direct(ext, N, m, misaligned, tt=2e-4):
+    # fp32 r2c rows that ops.fft.rfft_trunc cannot reach (it clamps m to
+    # N // 2 + 1, and hands over aligned tensors), through the entry point:
+    # the first m bins of the full spectrum of a real line
+    torch.manual_seed(14)
+    if misaligned:
+        x = torch.randn(_ROW_LINES * N + 1, device="cuda")[1:].view(_ROW_LINES, N)
+        assert x.data_ptr() % 16 == 4 and x.is_contiguous()
+    else:
+        x = torch.randn(_ROW_LINES, N, device="cuda")
+    y = ext.dft_rfft_trunc(x, 1, m)
+    yr = torch.fft.fft(x, dim=1)[:, :m]
+    assert torch.allclose(y, yr, rtol=tt, atol=tt * 10), f"fwd {(y-yr).abs().max()}"
+
+
+@pytest.mark.parametrize("acc", [False, True])
+@pytest.mark.parametrize("N,tt", [(64, 2e-4), (40, 2e-4), (128, 6e-4)])
+def test_dft_rfft_trunc_adj_rows_direct(ext, N, tt, acc, m=16):
+    # fp32 c2r rows: pinned (64, 16) and (40, 16), and the 128-line tiles of
+    # N = 128, each with and without the fused addend, against the autograd
+    # adjoint of the torch.fft composition
+    from dfno_amd.ops.fft import _t_rfft_trunc
+    torch.manual_seed(15)
+    gy = torch.randn(_ROW_LINES, m, device="cuda", dtype=torch.complex64)
+    xr = torch.zeros(_ROW_LINES, N, device="cuda", requires_grad=True)
+    _t_rfft_trunc(xr, 1, m).backward(gy)
+    ref = xr.grad
+    if acc:
+        a = torch.randn(_ROW_LINES, N, device="cuda")
+        gx = ext.dft_rfft_trunc_adj_acc(gy, 1, N, a)
+        ref = ref + a
+    else:
+        gx = ext.dft_rfft_trunc_adj(gy, 1, N)
+    assert torch.allclose(gx, ref, rtol=tt, atol=tt * 10), f"{(gx-ref).abs().max()}"
 
 
 @pytest.mark.parametrize("dtype,tt", [(torch.complex64, 3e-4), (torch.complex128, 1e-11)])
