@@ -31,7 +31,8 @@ SOURCES = [
     _CSRC / "dft.hip",
     _CSRC / "lift_head.hip",
     _CSRC / "pack.hip",
-    _CSRC / "bf16.hip",
+    _CSRC / "grad_w.hip",
+    _CSRC / "adam.hip",
     _CSRC / "dft2d.hip",
     _CSRC / "mix_bwd.hip",
     _CSRC / "epilogue.hip",

@@ -33,6 +33,7 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "launch_select.h"
 
 namespace {
 
@@ -942,19 +943,6 @@ __global__ __launch_bounds__(LB) void dft_c2r_last_kernel(
 // A new pinned length goes into select_pinned, a new mode cap into with_mcap,
 // a new IO type into the TI / TO parameter of launch_r2c / launch_c2r.
 // ---------------------------------------------------------------------------
-
-template <int V> using int_c = std::integral_constant<int, V>;
-
-// Calls f(int_c<V>) for the first candidate V that v fits (v <= V), or that
-// v equals when EXACT; false when there is none.
-template <bool EXACT, int... Vs, typename F>
-bool select_first(long v, F&& f) {
-  return (((EXACT ? v == Vs : v <= Vs) ? (f(int_c<Vs>{}), true) : false) || ...);
-}
-template <int... Vs, typename F>
-bool select_le(long v, F&& f) { return select_first<false, Vs...>(v, f); }
-template <int... Vs, typename F>
-bool select_eq(long v, F&& f) { return select_first<true, Vs...>(v, f); }
 
 // MCAP, the register cap of the kept-mode arrays (EXACT: m on a cap only)
 template <bool EXACT = false, typename F>

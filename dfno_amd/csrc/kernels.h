@@ -1,5 +1,5 @@
-// Host-visible declarations of the gfx950 HIP kernels (implemented in
-// pointwise.hip / spectral.hip, bound in bindings.cpp).
+// Host-visible declarations of the gfx950 HIP kernels (implemented in the
+// .hip files of this directory, bound in bindings.cpp).
 #pragma once
 
 #include <torch/extension.h>
@@ -76,8 +76,8 @@ std::vector<at::Tensor> proj_head_bwd_fused(const at::Tensor& gy,
                                             const at::Tensor& b3,
                                             const at::Tensor& W4);
 
-// split-s outer-product reduction: gW[o,i] = sum_{b,s} gz[b,o,s] x[b,i,s]
-// (+ gb[o] = sum gz when want_bias); requires I <= 64.
+// split-s outer-product reduction (grad_w.hip): gW[o,i] = sum_{b,s} gz[b,o,s]
+// x[b,i,s] (+ gb[o] = sum gz when want_bias); requires I <= 64.
 std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor& x,
                                           bool want_bias);
 
@@ -103,7 +103,7 @@ std::vector<at::Tensor> lift_head_bwd(const at::Tensor& gy, const at::Tensor& x,
                                       const at::Tensor& W1, const at::Tensor& b1,
                                       const at::Tensor& W2, const at::Tensor& b2);
 
-// fused Adam step on flat real views
+// fused Adam step on flat real views (adam.hip)
 void adam_step_(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Tensor& v,
                 double lr, double beta1, double beta2, double eps,
                 double weight_decay, int64_t step);
@@ -146,7 +146,7 @@ at::Tensor dft_rfft_trunc_adj_bf16(const at::Tensor& gy, int64_t dim,
                                    int64_t n, const at::Tensor& accum);
 
 // bf16-storage pointwise kernels (fp32 arithmetic; pointwise.hip, the
-// grad-W reduction in bf16.hip):
+// grad-W reduction in grad_w.hip):
 std::vector<at::Tensor> bf16_channel_mix(const at::Tensor& x, const at::Tensor& W,
                                          const at::Tensor& b, bool act, bool wt,
                                          bool write_z, const at::Tensor& res);

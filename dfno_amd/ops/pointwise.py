@@ -51,7 +51,7 @@ def _ebf(device):
 
 
 def _bf16_mix_ok(x3: torch.Tensor, I: int, O: int, op: str) -> bool:
-    """bf16-storage channel-mix kernel coverage (csrc/bf16.hip); shapes the
+    """bf16-storage channel-mix kernel coverage (csrc/pointwise.hip); shapes the
     wide kernel takes instead are not a fallback."""
     if not (x3.is_cuda and x3.dtype == torch.bfloat16):
         return False
@@ -73,6 +73,16 @@ def wide_mix_range(dtype, I: int, O: int, S: int) -> bool:
     if min(I, O) < 1 or not 33 <= max(I, O) <= 128:
         return False
     return dtype == torch.float32 or S % 8 == 0
+
+
+def grad_w_caps_ok(dtype, I: int, O: int, S: int) -> bool:
+    """The caps of the grad-W entry points (csrc/grad_w.hip), stated once, for
+    ``I`` x rows against ``O`` gz rows of length ``S``: the fp32 / fp64
+    reduction takes at most 64 x rows; the bf16 one also at most 128 gz rows,
+    in whole 128-element tiles."""
+    if dtype == torch.bfloat16:
+        return I <= 64 and O <= 128 and S % 128 == 0
+    return I <= 64
 
 
 def _wide_mix_ok(x3: torch.Tensor, I: int, O: int) -> bool:
@@ -136,18 +146,18 @@ def _mix_bwd_w(gz: torch.Tensor, x3: torch.Tensor, W: torch.Tensor,
                want_bias: bool):
     """gW[o,i] = sum_bs gz[b,o,s] x[b,i,s], gb[o] = sum_bs gz[b,o,s]."""
     I, O, S = x3.shape[1], W.shape[0], x3.shape[2]
-    bf16 = gz.is_cuda and gz.dtype == torch.bfloat16 and S % 128 == 0
-    if gz.is_cuda and _native_dt(gz) and I <= 64:
+    bf16 = gz.is_cuda and gz.dtype == torch.bfloat16
+    if gz.is_cuda and _native_dt(gz) and grad_w_caps_ok(gz.dtype, I, O, S):
         gW, gb = _ext.get(required=True).channel_mix_bwd_w(
             gz.contiguous(), x3.contiguous(), want_bias)
-    elif gz.is_cuda and _native_dt(gz) and O <= 64:
+    elif gz.is_cuda and _native_dt(gz) and grad_w_caps_ok(gz.dtype, O, I, S):
         # more than 64 x rows against few gz rows (linear4, 128 -> 1): the
         # same reduction with the roles swapped, gW^T[i,o] = sum x[i] gz[o]
         gWt, _ = _ext.get(required=True).channel_mix_bwd_w(
             x3.contiguous(), gz.contiguous(), False)
         gW = gWt.t().contiguous()
         gb = gz.sum(dim=(0, 2)) if want_bias else None
-    elif bf16 and I <= 64 and O <= 128:
+    elif bf16 and grad_w_caps_ok(gz.dtype, I, O, S):
         gW, gb = _ext.get(required=True).bf16_channel_mix_bwd_w(
             gz.contiguous(), x3.contiguous(), want_bias)
         gW, gb = gW.to(W.dtype), gb.to(W.dtype)

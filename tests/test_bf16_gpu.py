@@ -152,6 +152,32 @@ def test_bf16_grad_w_mfma(I, O, bias, S):
             f"bias max {(gb-refb).abs().max()}"
 
 
+@pytest.mark.parametrize("B,I,O,S,bias", [
+    # S = 384 is a multiple of 128 but not of 256: the LDS-tiled kernel
+    (1, 8, 8, 384, True),       # bf16_gw_kernel<1>
+    (2, 20, 128, 384, True),    # bf16_gw_kernel<4>, 4 o-slabs
+    (1, 20, 40, 384, False),    # bf16_gw_kernel<4>, ragged second slab (8 rows)
+])
+def test_bf16_grad_w_exact(B, I, O, S, bias):
+    """Integer-valued inputs in [-2, 2] are exact in bf16 and every partial
+    sum is an integer below 2^24, so the fp32-accumulated result must EQUAL
+    the fp64 einsum whatever the atomic order."""
+    ext = _ext()
+    g = torch.Generator().manual_seed(21)
+    gz = torch.randint(-2, 3, (B, O, S), generator=g).to("cuda", torch.bfloat16)
+    g.manual_seed(22)   # another stream for x: a transpose cannot pass
+    x = torch.randint(-2, 3, (B, I, S), generator=g).to("cuda", torch.bfloat16)
+    gW, gb = ext.bf16_channel_mix_bwd_w(gz, x, bias)
+    refW = torch.einsum("bos,bis->oi", gz.double(), x.double())
+    assert gW.dtype == torch.float32 and gW.shape == (O, I)
+    assert torch.equal(gW.double(), refW), \
+        f"{int((gW.double() != refW).sum())} of {O * I} entries differ"
+    if bias:
+        assert torch.equal(gb.double(), gz.double().sum(dim=(0, 2)))
+    else:
+        assert gb.numel() == 0
+
+
 def test_bf16_gelu_and_add_gelu():
     ext = _ext()
     torch.manual_seed(3)

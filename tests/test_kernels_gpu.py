@@ -123,6 +123,46 @@ def test_channel_mix_bwd_w(ext, dtype, B, I, O, S, bias):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("B,I,O,S,bias", [
+    # one shape per row of the grad-W launch table (the fp32 row is named;
+    # fp64 lands on the generic / i-slab non-vector rows)
+    (2, 16, 65, 256, False),     # gw_mfma_f32<2>, second o-slab of one row
+    (1, 40, 16, 132, True),      # i-slab, vector, OW 2, second slab of 8 rows
+    (1, 33, 5, 132, True),       # i-slab, vector, OW 1
+    (1, 33, 5, 130, False),      # i-slab, non-vector, OW 1
+    (2, 9, 8, 4100, False),      # glds3 <20,5,256>, 4 s-chunks, 4-element tail
+    (1, 2, 20, 4100, True),      # glds3 <8,4,256>, 2 o-tiles, chunks 4 -> 8
+    (1, 8, 128, 4100, False),    # glds3 <8,4,256>, 8 o-tiles, XCD swizzle
+    (1, 24, 24, 4100, True),     # glds3 <24,2,256>
+    (1, 32, 64, 4100, True),     # glds3 <32,2,128>, bias keeps it off MFMA
+    (1, 25, 12, 1284, False),    # glds3 <32,2,256>, chunks 1 -> 8, two empty
+    (2, 7, 9, 1003, True),       # generic cap 8 / OW 4, non-vector
+    (1, 20, 20, 1003, False),    # generic cap 24 / OW 2, non-vector
+    (1, 30, 10, 1003, True),     # generic cap 32 / OW 2, non-vector
+    (1, 20, 5, 1003, True),      # generic cap 32 / OW 1, non-vector
+    (1, 20, 5, 1000, False),     # generic cap 32 / OW 1, vector
+])
+def test_channel_mix_bwd_w_exact(ext, dtype, B, I, O, S, bias):
+    """Integer-valued inputs in [-2, 2]: every partial sum is an integer of
+    magnitude at most B * S * 4 <= 32800 < 2^24, so fp32 adds and fp32 MFMA
+    are exact in any order and the result must EQUAL the fp64 einsum.  A
+    dropped row, tile, chunk or tail element cannot hide in a tolerance."""
+    g = torch.Generator().manual_seed(11)
+    gz = torch.randint(-2, 3, (B, O, S), generator=g).to("cuda", dtype)
+    g.manual_seed(12)   # another stream for x: a transpose cannot pass
+    x = torch.randint(-2, 3, (B, I, S), generator=g).to("cuda", dtype)
+    gW, gb = ext.channel_mix_bwd_w(gz, x, bias)
+    refW = torch.einsum("bos,bis->oi", gz.double(), x.double())
+    assert gW.dtype == dtype and gW.shape == (O, I)
+    assert torch.equal(gW.double(), refW), \
+        f"{int((gW.double() != refW).sum())} of {O * I} entries differ"
+    if bias:
+        assert torch.equal(gb.double(), gz.double().sum(dim=(0, 2)))
+    else:
+        assert gb.numel() == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("B,I,O,S", [
     (2, 20, 20, 1003),  # the pinned block shape, odd S (element-wise tail)
     (1, 7, 9, 64),       # generic cap-8 kernel, float4 path in fp32

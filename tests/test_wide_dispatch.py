@@ -52,3 +52,18 @@ def test_cpu_tensors_never_take_it(dtype):
     x = torch.zeros(1, 64, 64, dtype=dtype)
     assert wide_mix_range(dtype, 64, 64, 64)
     assert not _wide_mix_ok(x, 64, 64)
+
+
+def test_grad_w_caps():
+    """The caps of the grad-W entry points as ops/pointwise.py states them:
+    64 x rows in fp32 / fp64 (gz rows unbounded, so the role swap asks with
+    the sides exchanged), and for bf16 also 128 gz rows and S % 128 == 0."""
+    from dfno_amd.ops.pointwise import grad_w_caps_ok
+    for dtype in (torch.float32, torch.float64):
+        assert grad_w_caps_ok(dtype, 64, 4096, 1003)
+        assert not grad_w_caps_ok(dtype, 65, 1, 1024)
+        assert grad_w_caps_ok(dtype, 1, 128, 777)      # linear4, roles swapped
+    assert grad_w_caps_ok(torch.bfloat16, 64, 128, 384)
+    assert not grad_w_caps_ok(torch.bfloat16, 65, 128, 384)
+    assert not grad_w_caps_ok(torch.bfloat16, 64, 129, 384)
+    assert not grad_w_caps_ok(torch.bfloat16, 20, 20, 1000)
