@@ -21,6 +21,9 @@ template <typename T> struct acc_of { using type = float; };
 template <> struct acc_of<double> { using type = double; };
 template <typename T> using acc_t = typename acc_of<T>::type;
 
+// accumulator fragment of v_mfma_f32_16x16x4_f32
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ float b2f(unsigned short h) {
   return __uint_as_float(((unsigned int)h) << 16);
 }
@@ -144,6 +147,11 @@ inline int launch_grid(long work, int block, long cap) {
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+// whether a float4 / uint4 access at p is aligned
+inline bool aligned16(const void* p) {
+  return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
 
 inline void check_real(const at::Tensor& t, const char* name) {

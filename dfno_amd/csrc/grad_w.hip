@@ -546,7 +546,6 @@ __global__ __launch_bounds__(kBlock) void bf16_gw_kernel(
 // ---------------------------------------------------------------------------
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bf16x8 load_frag(const unsigned short* row_base,
                                             long k0) {
@@ -727,10 +726,6 @@ void launch_gw_mfma(const GwCall& c) {
   DFNO_CHECK_LAUNCH("gw_mfma");
 }
 
-bool aligned16(const at::Tensor& t) {
-  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
-}
-
 }  // namespace
 
 std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor& x,
@@ -753,7 +748,7 @@ std::vector<at::Tensor> channel_mix_bwd_w(const at::Tensor& gz, const at::Tensor
 
   // vec: fp32 with whole, 16-byte aligned float4s in every row
   const bool vec = gz.scalar_type() == at::kFloat && S % 4 == 0 &&
-                   aligned16(gz) && aligned16(x);
+                   aligned16(gz.data_ptr()) && aligned16(x.data_ptr());
   // big-O shapes (the projection lift's gW3 [128, 20]) take the f32-MFMA tile
   // kernel; identical numerics (f32-in MFMA is a bitwise fmaf chain,
   // cdna_hip_programming.md section 3).  Bias only where the ones column

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "gelu_math.h"
 #include "device_util.h"
+#include "launch_select.h"
 
 namespace {
 
@@ -30,19 +31,20 @@ using namespace dfno_io;
 
 constexpr int kBlock = 256;
 
-typedef float f32x4_mb __attribute__((ext_vector_type(4)));
+constexpr int kTile = 64;          // s-columns per tile (16 MFMA K-steps)
 
 // TIO = unsigned short selects bf16 activations (fp32 compute; W and the
-// gW/gb accumulators stay fp32).  PH: phase mask for perf bisection
-// (1 staging+gz, +2 gx, +4 gW); production uses 7.  WX = false compiles
-// phase A (gx = W^T gz and its store) out: the caller applies W^T to the
-// streamed-back gz itself (rfft_adj_mix, epilogue.hip); gx is never touched.
-template <typename TIO, bool WG, int PH = 7, int TS = 64, bool WX = true>
+// gW/gb accumulators stay fp32).  WG streams the gz tile back to gzout.
+// WX = false compiles phase A (gx = W^T gz and its store) out: the caller
+// applies W^T to the streamed-back gz itself (rfft_adj_mix, epilogue.hip);
+// gx is never touched.
+template <typename TIO, bool WG, bool WX>
 __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
     const TIO* __restrict__ gy, const TIO* __restrict__ z,
     const TIO* __restrict__ x, const float* __restrict__ W,
     TIO* __restrict__ gx, float* __restrict__ gW, float* __restrict__ gb,
     TIO* __restrict__ gzout, int B, long S) {
+  constexpr int TS = kTile;
   constexpr int C = 20;            // in = out channels (trunk width)
   constexpr int LD = TS + 4;
   extern __shared__ __align__(16) char smem_raw[];
@@ -55,8 +57,8 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
   const int kg = lane >> 4;
 
   // gW/gb fragments: M = 2 o-tiles, N = 2 tiles (i channels + ones col)
-  f32x4_mb wacc;
-  wacc = f32x4_mb{0.f, 0.f, 0.f, 0.f};
+  f32x4 wacc;
+  wacc = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const long stiles = (S + TS - 1) / TS;
   const long tend = (long)B * stiles;
@@ -111,18 +113,16 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
     }
     prefetch(t + gridDim.x);
     __syncthreads();
-    constexpr bool kPhaseA = WX && (PH & 2) != 0;
-    if constexpr (!kPhaseA && (PH & 4) == 0) continue;
     // phase A: gx = W^T @ gz.  A[m=i][k=o] = W[o*C+i] (per-lane global,
     // L1-resident), B[n=c][k=o] = gzt[o][c]; K = C padded to 24.
 #pragma unroll
-    for (int pp = 0; pp < (kPhaseA ? (2 * (TS / 16)) / 4 : 0); ++pp) {
+    for (int pp = 0; pp < (WX ? (2 * (TS / 16)) / 4 : 0); ++pp) {
       const int p = wave + 4 * pp;
       const int mt = p / (TS / 16), nt = p % (TS / 16);
       const int m = mt * 16 + l16;
       const int n = nt * 16 + l16;
       const bool av = m < C;
-      f32x4_mb c4 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k = 0; k < C; k += 4) {       // C = 20: K is 4-aligned
         const int ko = k + kg;
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
     // phase B: gW fragments += gz @ [x; ones]^T.  One (mt, nt) pair per
     // wave: mt = wave>>1 (o-tiles), nt = wave&1 (i-tiles; col C = ones
     // for gb).
-    if constexpr ((PH & 4) != 0) {
+    {
       const int mt = wave >> 1, nt = wave & 1;
       const float* gr = gzt + (mt * 16 + l16) * LD;
       const int ncol = nt * 16 + l16;
@@ -173,6 +173,28 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
       }
     }
   }
+}
+
+// One launch of mix_bwd_fused_kernel<TIO, WG, WX>: grid-stride over the
+// B * ceil(S / 64) tiles with at most 1024 blocks (4 per CU), the gz and x
+// tiles [20][68] fp32 in dynamic LDS.  An output the instantiation never
+// stores (gz without WG, gx without WX) goes in as null.
+template <typename TIO, bool WG, bool WX>
+void launch_mix_bwd(const at::Tensor& gy, const at::Tensor& z,
+                    const at::Tensor& x, const at::Tensor& W, at::Tensor& gx,
+                    at::Tensor& gW, float* gb, at::Tensor& gz, int B, long S) {
+  const long stiles = (S + kTile - 1) / kTile;
+  const int grid = (int)std::min((long)B * stiles, 1024L);
+  const size_t smem = sizeof(float) * 2 * 20 * (kTile + 4);
+  hipLaunchKernelGGL((mix_bwd_fused_kernel<TIO, WG, WX>), dim3(grid),
+                     dim3(kBlock), smem,
+                     at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(),
+                     static_cast<const TIO*>(gy.data_ptr()),
+                     static_cast<const TIO*>(z.data_ptr()),
+                     static_cast<const TIO*>(x.data_ptr()), W.data_ptr<float>(),
+                     WX ? static_cast<TIO*>(gx.data_ptr()) : nullptr,
+                     gW.data_ptr<float>(), gb,
+                     WG ? static_cast<TIO*>(gz.data_ptr()) : nullptr, B, S);
 }
 
 }  // namespace
@@ -210,66 +232,21 @@ std::vector<at::Tensor> channel_mix_bwd_fused(const at::Tensor& gy,
                     : at::empty({0}, x.options());
   if (x.numel() == 0) return {gx, gW, gb, gz};
 
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  static const bool ts128 = []() {
-    const char* e = getenv("DFNO_MIX_TS128");    // tile-size A/B knob
-    return e && e[0] == '1';
-  }();
-  const int TS = ts128 ? 128 : 64;
-  size_t smem = sizeof(float) * 2 * 20 * (TS + 4);
-  long stiles = (S + TS - 1) / TS;
-  int grid = (int)std::min((long)B * stiles, 1024L);
+  // Rows: {fp32, bf16} x (gz and gx | gx only | gz only); gz only is the
+  // WX = false kernel without phase A.
   float* gbp = want_bias ? gb.data_ptr<float>() : nullptr;
-  static const int ph = []() {
-    const char* e = getenv("DFNO_MIX_PHASES");   // perf-bisect knob
-    return e ? atoi(e) : 7;
-  }();
-#define MB_LAUNCH(TIO, WG, GZP) MB_LAUNCH_T(TIO, WG, GZP, 7, 64)
-#define MB_LAUNCH_P(TIO, WG, GZP, PHV) MB_LAUNCH_T(TIO, WG, GZP, PHV, 64)
-#define MB_LAUNCH_T(TIO, WG, GZP, PHV, TSV)                                  \
-  hipLaunchKernelGGL((mix_bwd_fused_kernel<TIO, WG, PHV, TSV>), dim3(grid), \
-                     dim3(kBlock), smem, stream,                             \
-                     reinterpret_cast<const TIO*>(gy.data_ptr()),            \
-                     reinterpret_cast<const TIO*>(z.data_ptr()),             \
-                     reinterpret_cast<const TIO*>(x.data_ptr()),             \
-                     W.data_ptr<float>(),                                    \
-                     reinterpret_cast<TIO*>(gx.data_ptr()),                  \
-                     gW.data_ptr<float>(), gbp, GZP, B, S)
-  // gz + gW only: phase A is compiled out, so gx is never stored through
-#define MB_LAUNCH_NOGX(TIO, GZP)                                             \
-  hipLaunchKernelGGL((mix_bwd_fused_kernel<TIO, true, 7, 64, false>),       \
-                     dim3(grid), dim3(kBlock), smem, stream,                 \
-                     reinterpret_cast<const TIO*>(gy.data_ptr()),            \
-                     reinterpret_cast<const TIO*>(z.data_ptr()),             \
-                     reinterpret_cast<const TIO*>(x.data_ptr()),             \
-                     W.data_ptr<float>(), static_cast<TIO*>(nullptr),        \
-                     gW.data_ptr<float>(), gbp, GZP, B, S)
-  if (!want_gx) {
-    if (bf16)
-      MB_LAUNCH_NOGX(unsigned short,
-                     reinterpret_cast<unsigned short*>(gz.data_ptr()));
-    else
-      MB_LAUNCH_NOGX(float, reinterpret_cast<float*>(gz.data_ptr()));
-  } else if (bf16) {
-    auto gzp = want_gz ? reinterpret_cast<unsigned short*>(gz.data_ptr())
-                       : nullptr;
-    if (want_gz) MB_LAUNCH(unsigned short, true, gzp);
-    else         MB_LAUNCH(unsigned short, false, nullptr);
-  } else {
-    auto gzp = want_gz ? reinterpret_cast<float*>(gz.data_ptr()) : nullptr;
-    if (want_gz) {
-      if (ts128) { MB_LAUNCH_T(float, true, gzp, 7, 128); }
-      else if (ph == 1) { MB_LAUNCH_T(float, true, gzp, 1, 64); }
-      else if (ph == 3) { MB_LAUNCH_T(float, true, gzp, 3, 64); }
-      else if (ph == 5) { MB_LAUNCH_T(float, true, gzp, 5, 64); }
-      else { MB_LAUNCH_T(float, true, gzp, 7, 64); }
-    }
-    else         MB_LAUNCH(float, false, nullptr);
-  }
-#undef MB_LAUNCH_NOGX
-#undef MB_LAUNCH_T
-#undef MB_LAUNCH_P
-#undef MB_LAUNCH
+  auto go = [&](auto elem) {            // storage type, by example
+    using TIO = decltype(elem);
+    select_bool(want_gz, [&](auto wg) {
+      select_bool(want_gx, [&](auto wx) {
+        constexpr bool WG = decltype(wg)::value, WX = decltype(wx)::value;
+        if constexpr (WG || WX)
+          launch_mix_bwd<TIO, WG, WX>(gy, z, x, W, gx, gW, gbp, gz, B, S);
+      });
+    });
+  };
+  if (bf16) go((unsigned short)0); else go(0.f);
   DFNO_CHECK_LAUNCH("mix_bwd_fused");
   return {gx, gW, gb, gz};
 }
+

@@ -404,10 +404,6 @@ void launch_wide(const WideArgs<T>& a) {
   }
 }
 
-bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
-
 }  // namespace
 
 std::vector<at::Tensor> wide_channel_mix(const at::Tensor& x, const at::Tensor& W,

@@ -397,8 +397,7 @@ struct MixLaunch {
 bool can_vectorize(const float* x, const float* y, const float* z, long S,
                    bool write_z) {
   if (S % 4 != 0) return false;
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return aligned(x) && aligned(y) && (!write_z || aligned(z));
+  return aligned16(x) && aligned16(y) && (!write_z || aligned16(z));
 }
 bool can_vectorize(const double*, const double*, const double*, long, bool) {
   return false;

@@ -1,7 +1,7 @@
 // gfx950 fused FNO projection head: out = W4 @ gelu(W3 @ x + b3) + b4.
 //
 // The reference computes this as two BroadcastedLinear einsums with a
-// separate GELU between (/root/reference/dfno/dfno.py:348-352), which at the
+// separate GELU between (dfno.py:348-352), which at the
 // flagship config materializes a [1,128,64^3*30] fp32 intermediate (~4 GB)
 // three times over (einsum out, bias add, gelu out).  On MI355X that is
 // ~25 GB of pointless HBM traffic per forward (and ~2x in backward).
@@ -28,14 +28,13 @@
 #include "kernels.h"
 #include "gelu_math.h"
 #include "device_util.h"
+#include "launch_select.h"
 
 namespace {
 
 using namespace dfno_io;
 
 constexpr int kBlock = 256;
-
-typedef float f32x4_ph __attribute__((ext_vector_type(4)));
 
 template <typename T, int IMAX, int O2MAX, int VEC, bool VECTOR,
           int MT = 0, int IT = 0, typename TIO = T>
@@ -70,19 +69,19 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
-        const float4 v = *reinterpret_cast<const float4*>(
-            reinterpret_cast<const float*>(xb) + (long)i * S);
-        xr[i][0] = v.x; xr[i][1] = v.y; xr[i][2] = v.z; xr[i][3] = v.w;
-              }
+          const float4 v = *reinterpret_cast<const float4*>(
+              reinterpret_cast<const float*>(xb) + (long)i * S);
+          xr[i][0] = v.x; xr[i][1] = v.y; xr[i][2] = v.z; xr[i][3] = v.w;
+        }
       }
     } else {
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k)
-          xr[i][k] = (full || k < nv) ? (T)ld(xb + (long)i * S + k) : T(0);
-              }
+          for (int k = 0; k < VEC; ++k)
+            xr[i][k] = (full || k < nv) ? (T)ld(xb + (long)i * S + k) : T(0);
+        }
       }
     }
 
@@ -91,8 +90,8 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
     for (int o = 0; o < O2MAX; ++o) {
       if (o < O2) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) acc[o][k] = b4l[o];
-          }
+        for (int k = 0; k < VEC; ++k) acc[o][k] = b4l[o];
+      }
     }
 
 #pragma unroll 8
@@ -105,20 +104,20 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
-        T wv = W3l[(size_t)j * I + i];
+          T wv = W3l[(size_t)j * I + i];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) zk[k] += wv * xr[i][k];
-              }
+          for (int k = 0; k < VEC; ++k) zk[k] += wv * xr[i][k];
+        }
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) zk[k] = dfno_gelu::gelu(zk[k]);
 #pragma unroll
       for (int o = 0; o < O2MAX; ++o) {
         if (o < O2) {
-        T w4 = W4l[(size_t)o * M + j];
+          T w4 = W4l[(size_t)o * M + j];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[o][k] += w4 * zk[k];
-              }
+          for (int k = 0; k < VEC; ++k) acc[o][k] += w4 * zk[k];
+        }
       }
     }
 
@@ -126,141 +125,18 @@ __global__ __launch_bounds__(kBlock) void proj_head_fwd_kernel(
 #pragma unroll
     for (int o = 0; o < O2MAX; ++o) {
       if (o < O2) {
-      if constexpr (VECTOR && std::is_same<T, float>::value &&
-                    std::is_same<TIO, float>::value) {
-        *reinterpret_cast<float4*>(
-            reinterpret_cast<float*>(ob) + (long)o * S) =
-            make_float4(acc[o][0], acc[o][1], acc[o][2], acc[o][3]);
-      } else {
+        if constexpr (VECTOR && std::is_same<T, float>::value &&
+                      std::is_same<TIO, float>::value) {
+          *reinterpret_cast<float4*>(
+              reinterpret_cast<float*>(ob) + (long)o * S) =
+              make_float4(acc[o][0], acc[o][1], acc[o][2], acc[o][3]);
+        } else {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          if (!full && k >= nv) break;
-          st(ob + (long)o * S + k, acc[o][k]);
-        }
-      }
+          for (int k = 0; k < VEC; ++k) {
+            if (!full && k >= nv) break;
+            st(ob + (long)o * S + k, acc[o][k]);
           }
-    }
-  }
-}
-
-// Tiled MFMA forward for the flagship head (I=20, M=128, O2<=2): the
-// per-thread kernel above walks all 128 hidden channels per element
-// (VALU z3 + scalar-broadcast weights) and measures ~1.04 ms; here z3
-// runs as v_mfma_f32_16x16x4 over a [128 x 64] LDS tile, gelu is applied
-// in place, and the W4 contraction is one thin MFMA M-tile (rows 0..O2-1
-// of a padded 16-row A).  TIO = unsigned short selects bf16 activations.
-template <int IT, int MT, int O2T, typename TIO = float>
-__global__ __launch_bounds__(kBlock, 3) void proj_head_fwd_fused_kernel(
-    const TIO* __restrict__ x, const float* __restrict__ W3,
-    const float* __restrict__ b3, const float* __restrict__ W4,
-    const float* __restrict__ b4, TIO* __restrict__ out,
-    int B, int O2, long S) {
-  constexpr int TS = 64;
-  constexpr int LD = TS + 4;
-  extern __shared__ __align__(16) char smem_raw[];
-  float* ht = reinterpret_cast<float*>(smem_raw);    // [MT][LD]
-  float* xt = ht + (size_t)MT * LD;                  // [IT][LD]
-  float* W3l = xt + (size_t)IT * LD;                 // [MT*IT]
-  float* b3l = W3l + (size_t)MT * IT;                // [MT]
-  float* W4l = b3l + MT;                             // [O2T*MT]
-#pragma clang loop unroll(disable)
-  for (int k = threadIdx.x; k < MT * IT; k += kBlock) W3l[k] = W3[k];
-  for (int k = threadIdx.x; k < MT; k += kBlock) b3l[k] = b3[k];
-  for (int k = threadIdx.x; k < O2T * MT; k += kBlock) W4l[k] = W4[k];
-
-  const int lane = (int)(threadIdx.x & 63);
-  const int wave = (int)(threadIdx.x >> 6);
-  const int l16 = lane & 15;
-  const int kg = lane >> 4;
-
-  const long stiles = (S + TS - 1) / TS;
-  const long tend = (long)B * stiles;
-  constexpr int NPF = (IT * TS + kBlock - 1) / kBlock;
-  float pf[NPF];
-  auto prefetch = [&](long tt) {
-    if (tt >= tend) return;
-    const int b = (int)(tt / stiles);
-    const long s0 = (tt % stiles) * TS;
-    const int nv = (int)min((long)TS, S - s0);
-#pragma unroll
-    for (int q = 0; q < NPF; ++q) {
-      const int r = (int)threadIdx.x + q * kBlock;
-      if (r >= IT * TS) break;
-      const int row = r / TS;
-      const int c = r - row * TS;
-      pf[q] = (c < nv) ? ld(x + ((long)b * IT + row) * S + s0 + c) : 0.f;
-    }
-  };
-  prefetch(blockIdx.x);
-
-  for (long t = blockIdx.x; t < tend; t += gridDim.x) {
-    const int b = (int)(t / stiles);
-    const long s0 = (t % stiles) * TS;
-    __syncthreads();               // prior tile's phase reads done
-#pragma unroll
-    for (int q = 0; q < NPF; ++q) {
-      const int r = (int)threadIdx.x + q * kBlock;
-      if (r >= IT * TS) break;
-      const int row = r / TS;
-      const int c = r - row * TS;
-      xt[row * LD + c] = pf[q];
-    }
-    prefetch(t + gridDim.x);
-    __syncthreads();
-    // phase 1: z3 tile = W3 @ x (8 m-tiles x 4 n-tiles, K = IT)
-#pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-      const int p = wave + 4 * pp;
-      const int mt = p >> 2, nt = p & 3;
-      const int m = mt * 16 + l16;
-      const int n = nt * 16 + l16;
-      f32x4_ph z4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < IT; k += 4) {
-        const float a = W3l[m * IT + k + kg];
-        const float bb = xt[(k + kg) * LD + n];
-        z4 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, z4, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        ht[(mt * 16 + kg * 4 + r) * LD + nt * 16 + l16] = z4[r];
-    }
-    __syncthreads();
-    // phase 2: h = gelu(z3 + b3) in place (pair of threads per channel)
-    {
-      const int jj = (int)(threadIdx.x >> 1);
-      const int half = (int)(threadIdx.x & 1) * 4;
-      const float bj = b3l[jj];
-#pragma unroll
-      for (int k = 0; k < TS / 8; ++k) {
-        const int c4 = half + k * 8;
-        float4 zv = *reinterpret_cast<float4*>(ht + jj * LD + c4);
-        zv.x = dfno_gelu::gelu(zv.x + bj);
-        zv.y = dfno_gelu::gelu(zv.y + bj);
-        zv.z = dfno_gelu::gelu(zv.z + bj);
-        zv.w = dfno_gelu::gelu(zv.w + bj);
-        *reinterpret_cast<float4*>(ht + jj * LD + c4) = zv;
-      }
-    }
-    __syncthreads();
-    // phase 3: out = W4 @ h + b4 — one thin MFMA tile (A rows 0..O2-1
-    // hold W4, the rest zero); wave = n-tile
-    {
-      const int n = wave * 16 + l16;
-      f32x4_ph c4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-      for (int k = 0; k < MT; k += 4) {
-        float a = 0.f;
-        if (l16 == 0) a = W4l[k + kg];
-        else if (O2T == 2 && l16 == 1) a = W4l[MT + k + kg];
-        const float bb = ht[(k + kg) * LD + n];
-        c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, c4, 0, 0, 0);
-      }
-      const long sc = s0 + n;
-      if (kg == 0 && sc < S) {
-#pragma unroll
-        for (int r = 0; r < O2T; ++r)
-          st(out + ((long)b * O2T + r) * S + sc, c4[r] + b4[r]);
+        }
       }
     }
   }
@@ -318,33 +194,33 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
-        const float4 v = *reinterpret_cast<const float4*>(xb + (long)i * S);
-        xr[i][0] = v.x; xr[i][1] = v.y; xr[i][2] = v.z; xr[i][3] = v.w;
-              }
+          const float4 v = *reinterpret_cast<const float4*>(xb + (long)i * S);
+          xr[i][0] = v.x; xr[i][1] = v.y; xr[i][2] = v.z; xr[i][3] = v.w;
+        }
       }
 #pragma unroll
       for (int o = 0; o < O2MAX; ++o) {
         if (o < O2) {
-        const float4 v = *reinterpret_cast<const float4*>(gyb + (long)o * S);
-        gyv[o][0] = v.x; gyv[o][1] = v.y; gyv[o][2] = v.z; gyv[o][3] = v.w;
-              }
+          const float4 v = *reinterpret_cast<const float4*>(gyb + (long)o * S);
+          gyv[o][0] = v.x; gyv[o][1] = v.y; gyv[o][2] = v.z; gyv[o][3] = v.w;
+        }
       }
     } else {
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k)
-          xr[i][k] = (full || k < nv) ? xb[(long)i * S + k] : T(0);
-              }
+          for (int k = 0; k < VEC; ++k)
+            xr[i][k] = (full || k < nv) ? xb[(long)i * S + k] : T(0);
+        }
       }
 #pragma unroll
       for (int o = 0; o < O2MAX; ++o) {
         if (o < O2) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k)
-          gyv[o][k] = (full || k < nv) ? gyb[(long)o * S + k] : T(0);
-              }
+          for (int k = 0; k < VEC; ++k)
+            gyv[o][k] = (full || k < nv) ? gyb[(long)o * S + k] : T(0);
+        }
       }
     }
 
@@ -352,8 +228,8 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
     for (int o = 0; o < O2MAX; ++o) {
       if (o < O2) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) gb4acc[o] += gyv[o][k];
-          }
+        for (int k = 0; k < VEC; ++k) gb4acc[o] += gyv[o][k];
+      }
     }
 
 
@@ -369,10 +245,10 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
 #pragma unroll
       for (int i = 0; i < IMAX; ++i) {
         if (i < I) {
-        T wv = W3l[(size_t)j * I + i];
+          T wv = W3l[(size_t)j * I + i];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) zk[k] += wv * xr[i][k];
-              }
+          for (int k = 0; k < VEC; ++k) zk[k] += wv * xr[i][k];
+        }
       }
       T gk[VEC], dgk[VEC];
 #pragma unroll
@@ -385,10 +261,10 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
 #pragma unroll
       for (int o = 0; o < O2MAX; ++o) {
         if (o < O2) {
-        T w4 = W4l[(size_t)o * M + j];
+          T w4 = W4l[(size_t)o * M + j];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) gzk[k] += w4 * gyv[o][k];
-              }
+          for (int k = 0; k < VEC; ++k) gzk[k] += w4 * gyv[o][k];
+        }
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) gzk[k] *= dgk[k];
@@ -413,12 +289,12 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
 #pragma unroll
       for (int o = 0; o < O2MAX; ++o) {
         if (o < O2) {
-        T pw = T(0);
+          T pw = T(0);
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) pw += (full || k < nv) ? gyv[o][k] * gk[k] : T(0);
-        pw = wave_sum(pw);
-        if (lane == 0) gW4w[(wave * O2 + o) * M + j] += pw;
-              }
+          for (int k = 0; k < VEC; ++k) pw += (full || k < nv) ? gyv[o][k] * gk[k] : T(0);
+          pw = wave_sum(pw);
+          if (lane == 0) gW4w[(wave * O2 + o) * M + j] += pw;
+        }
       }
     }
 
@@ -428,9 +304,9 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
 #pragma unroll
   for (int o = 0; o < O2MAX; ++o) {
     if (o < O2) {
-    T v = wave_sum(gb4acc[o]);
-    if (lane == 0 && v != T(0)) atomicAdd(&gb4[o], v);
-      }
+      T v = wave_sum(gb4acc[o]);
+      if (lane == 0 && v != T(0)) atomicAdd(&gb4[o], v);
+    }
   }
   __syncthreads();
   for (int k = threadIdx.x; k < M; k += blockDim.x) {
@@ -493,9 +369,9 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
   const int l16 = lane & 15;
   const int kg = lane >> 4;
 
-  f32x4_ph wacc[4];                // gW3 frags: 8 mt-tiles x 2 nt-tiles
+  f32x4 wacc[4];                // gW3 frags: 8 mt-tiles x 2 nt-tiles
 #pragma unroll
-  for (int p = 0; p < 4; ++p) wacc[p] = f32x4_ph{0.f, 0.f, 0.f, 0.f};
+  for (int p = 0; p < 4; ++p) wacc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
   float gb4a0 = 0.f, gb4a1 = 0.f;
 
   const long stiles = (S + TS - 1) / TS;
@@ -553,7 +429,7 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
       const int mt = p >> 2, nt = p & 3;
       const int m = mt * 16 + l16;
       const int n = nt * 16 + l16;
-      f32x4_ph z4 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k = 0; k < IT; k += 4) {
         const float a = W3l[m * IT + k + kg];
@@ -620,7 +496,7 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
       const int m = mt * 16 + l16;
       const int n = nt * 16 + l16;
       const bool av = m < IT;
-      f32x4_ph c4 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
       for (int k = 0; k < MT; k += 4) {
         const float a = av ? W3l[(k + kg) * IT + m] : 0.f;
@@ -681,189 +557,175 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
     if (gW4s[k] != 0.f) atomicAdd(&gW4[k], gW4s[k]);
 }
 
-template <typename T>
-bool vec_ok(long S, std::initializer_list<const void*> ptrs) {
-  if (!std::is_same<T, float>::value) return false;
-  if (S % 4 != 0) return false;
-  for (auto p : ptrs)
-    if ((reinterpret_cast<uintptr_t>(p) & 15) != 0) return false;
-  return true;
+// ---- host side ----
+
+// x [B,I,S], W3 [M,I], b3 [M], W4 [O2,M] and b4 [O2] (forward) or gy [B,O2,S]
+// (backward).  I and O2 size the per-thread register tiles, M the hidden
+// walk and, with them, the LDS of proj_head_bwd_kernel: an out-of-range call
+// raises in proj_dims, never launches.
+struct ProjDims {
+  int B, I, M, O2;
+  long S;
+  // the shape with compile-time M / I kernels, the bf16 forward and the
+  // fused backward
+  bool pinned() const { return I == 20 && M == 128 && O2 <= 2; }
+  // dynamic LDS of proj_head_bwd_kernel, in its layout order: W3l [M*I],
+  // b3l [M], W4l [O2*M], the per-wave partials gb3w [4*M] and gW4w [4*O2*M]
+  // (ops/projhead.py, proj_head_bwd_lds, states the same sum)
+  size_t bwd_lds(size_t elem) const {
+    const size_t m = (size_t)M;
+    return elem * (m * I + m + O2 * m + 4 * m + 4 * O2 * m);
+  }
+};
+constexpr size_t kBwdLdsLimit = 160 * 1024;
+
+ProjDims proj_dims(const at::Tensor& x, const at::Tensor& W3,
+                   const at::Tensor& b3, const at::Tensor& W4,
+                   const at::Tensor& last, bool last_is_gy) {
+  const auto st = x.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kDouble || st == at::kBFloat16,
+              "proj_head: x must be float32/float64/bfloat16");
+  TORCH_CHECK(x.dim() == 3 && W3.dim() == 2 && b3.dim() == 1 && W4.dim() == 2,
+              "proj_head: x [B,I,S], W3 [M,I], b3 [M], W4 [O2,M]");
+  for (const at::Tensor* t : {&x, &W3, &b3, &W4, &last}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == st,
+                "proj_head: contiguous GPU tensors of one dtype");
+  }
+  const long B = x.size(0), I = x.size(1), S = x.size(2);
+  const long M = W3.size(0), O2 = W4.size(0);
+  TORCH_CHECK(W3.size(1) == I && b3.size(0) == M && W4.size(1) == M,
+              "proj_head shapes");
+  if (last_is_gy) {
+    TORCH_CHECK(last.dim() == 3 && last.size(0) == B && last.size(1) == O2 &&
+                last.size(2) == S, "proj_head: gy must be [B,O2,S]");
+  } else {
+    TORCH_CHECK(last.dim() == 1 && last.size(0) == O2, "proj_head shapes");
+  }
+  TORCH_CHECK(I >= 1 && I <= 32 && O2 >= 1 && O2 <= 8 && M >= 1 && M <= 512,
+              "proj_head: unsupported dims (I <= 32, M <= 512, O2 <= 8)");
+  TORCH_CHECK(B < (1L << 31), "proj_head: batch too large");
+  return {(int)B, (int)I, (int)M, (int)O2, S};
 }
+
+// Rows of the per-thread kernels, first match wins:
+//   pinned 20 -> 128 -> (<= 2)   <IMAX 24, O2MAX 2, MT 128, IT 20>
+//   I <= 24, O2 <= 2             <24, 2>, runtime M / I
+//   the rest, to the caps        <32, 8>, runtime M / I
+// each with VECTOR (float4 IO: fp32, S % 4 == 0, 16-byte aligned bases) or
+// element-wise; fp64 has the element-wise form only and bf16 IO only the
+// pinned element-wise forward (its backward is proj_head_bwd_fused).
+struct ProjRow { int imax, o2max, mt, it; };
+constexpr ProjRow kProjRows[] = {{24, 2, 128, 20}, {24, 2, 0, 0}, {32, 8, 0, 0}};
+
+template <typename F>
+void with_proj_row(const ProjDims& d, F&& f) {
+  const int row = d.pinned() ? 0 : (d.I <= 24 && d.O2 <= 2) ? 1 : 2;
+  select_eq<0, 1, 2>(row, f);
+}
+template <typename T, typename F>
+void with_vector(bool vec, F&& f) {
+  if constexpr (std::is_same_v<T, float>) select_bool(vec, f);
+  else f(std::false_type{});
+}
+
+// both per-thread kernels: one thread per 4 s-columns, at most 8 blocks per CU
+int proj_grid(const ProjDims& d) {
+  return launch_grid((long)d.B * ((d.S + 3) / 4), kBlock, 256L * 8);
+}
+
+// T: math and weight type, TIO: storage type of x / out
+template <typename T, typename TIO>
+void launch_proj_fwd(const ProjDims& d, const at::Tensor& x,
+                     const at::Tensor& W3, const at::Tensor& b3,
+                     const at::Tensor& W4, const at::Tensor& b4,
+                     at::Tensor& out) {
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  auto launch = [&](auto r, auto v) {
+    constexpr ProjRow R = kProjRows[decltype(r)::value];
+    hipLaunchKernelGGL(
+        (proj_head_fwd_kernel<T, R.imax, R.o2max, 4, decltype(v)::value, R.mt,
+                              R.it, TIO>),
+        dim3(proj_grid(d)), dim3(kBlock), 0, stream,
+        static_cast<const TIO*>(x.data_ptr()), W3.data_ptr<T>(),
+        b3.data_ptr<T>(), W4.data_ptr<T>(), b4.data_ptr<T>(),
+        static_cast<TIO*>(out.data_ptr()), d.B, d.I, d.M, d.O2, d.S);
+  };
+  if constexpr (!std::is_same_v<T, TIO>) {
+    launch(int_c<0>{}, std::false_type{});     // bf16 IO: the pinned row
+  } else {
+    const bool vec = d.S % 4 == 0 && aligned16(x.data_ptr()) &&
+                     aligned16(out.data_ptr());
+    with_proj_row(d, [&](auto r) {
+      with_vector<T>(vec, [&](auto v) { launch(r, v); });
+    });
+  }
+  DFNO_CHECK_LAUNCH("proj_head");
+}
+
+template <typename T>
+void launch_proj_bwd(const ProjDims& d, const at::Tensor& gy,
+                     const at::Tensor& x, const at::Tensor& W3,
+                     const at::Tensor& b3, const at::Tensor& W4,
+                     at::Tensor& gz3, at::Tensor& gb3, at::Tensor& gW4,
+                     at::Tensor& gb4) {
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const bool vec = d.S % 4 == 0 && aligned16(x.data_ptr()) &&
+                   aligned16(gy.data_ptr()) && aligned16(gz3.data_ptr());
+  with_proj_row(d, [&](auto r) {
+    with_vector<T>(vec, [&](auto v) {
+      constexpr ProjRow R = kProjRows[decltype(r)::value];
+      hipLaunchKernelGGL(
+          (proj_head_bwd_kernel<T, R.imax, R.o2max, 4, decltype(v)::value, R.mt,
+                                R.it>),
+          dim3(proj_grid(d)), dim3(kBlock), d.bwd_lds(sizeof(T)), stream,
+          gy.data_ptr<T>(), x.data_ptr<T>(), W3.data_ptr<T>(),
+          b3.data_ptr<T>(), W4.data_ptr<T>(), gz3.data_ptr<T>(),
+          gb3.data_ptr<T>(), gW4.data_ptr<T>(), gb4.data_ptr<T>(), d.B, d.I,
+          d.M, d.O2, d.S);
+    });
+  });
+  DFNO_CHECK_LAUNCH("proj_head");
+}
+
+// fp32 staging copy of a bf16 weight (the tensor itself when it is fp32)
+at::Tensor f32(const at::Tensor& t) { return t.to(at::kFloat); }
 
 }  // namespace
 
 at::Tensor proj_head_fwd(const at::Tensor& x, const at::Tensor& W3,
                          const at::Tensor& b3, const at::Tensor& W4,
                          const at::Tensor& b4) {
+  const ProjDims d = proj_dims(x, W3, b3, W4, b4, false);
   const bool bf16 = x.scalar_type() == at::kBFloat16;
-  if (!bf16) { check_real(x, "x"); }
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "x must be contiguous GPU");
-  TORCH_CHECK(x.dim() == 3, "x must be [B,I,S]");
-  int B = (int)x.size(0), I = (int)x.size(1);
-  long S = x.size(2);
-  int M = (int)W3.size(0), O2 = (int)W4.size(0);
-  TORCH_CHECK((int)W3.size(1) == I && (int)W4.size(1) == M, "proj_head shapes");
-  TORCH_CHECK(I <= 32 && O2 <= 8 && M <= 512, "proj_head: unsupported dims");
-
-  auto out = at::empty({B, O2, S}, x.options());
+  TORCH_CHECK(!bf16 || d.pinned(), "proj_head_fwd: flagship shape only");
+  auto out = at::empty({d.B, d.O2, d.S}, x.options());
   if (x.numel() == 0) return out;
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = launch_grid((long)B * ((S + 3) / 4), kBlock, 256L * 8);
-  // The tiled-MFMA forward below is correct but measured SLOWER than the
-  // register-resident per-thread kernel (1.48 vs 1.06 ms within-process
-  // A/B at the flagship): the z3 tile costs 4 LDS passes + 3 barriers
-  // that the per-thread scheme (weights via s_loads, z/h/out all in
-  // registers) never pays; the per-thread bf16-IO variant likewise wins
-  // for bf16 (1.15 vs ~1.6 ms).  Kept as an opt-in (DFNO_PF_FUSED=1)
-  // for shapes where the VALU z3 walk dominates.
-  static const bool want_fused_fwd = []() {
-    const char* e = getenv("DFNO_PF_FUSED");   // A/B knob
-    return e && e[0] == '1';
-  }();
-  if (want_fused_fwd && I == 20 && M == 128 && O2 <= 2 &&
-      (bf16 || x.scalar_type() == at::kFloat)) {
-    // flagship: tiled MFMA forward (z3 as 16x16x4 fragments over a
-    // [128 x 64] LDS tile instead of per-thread hidden-channel walks)
-    auto W3f = bf16 ? W3.to(at::kFloat).contiguous() : W3.contiguous();
-    auto b3f = bf16 ? b3.to(at::kFloat).contiguous() : b3.contiguous();
-    auto W4f = bf16 ? W4.to(at::kFloat).contiguous() : W4.contiguous();
-    auto b4f = bf16 ? b4.to(at::kFloat).contiguous() : b4.contiguous();
-    constexpr int TS = 64, LD = TS + 4;
-    size_t smem = sizeof(float) *
-        ((size_t)128 * LD + 20 * LD + (size_t)128 * 20 + 128 +
-         2 * (size_t)128);
-    long stiles = (S + TS - 1) / TS;
-    int grid2 = (int)std::min((long)B * stiles, 768L);
-#define PH_FWD_F(O2T, TIO)                                                    \
-    hipLaunchKernelGGL((proj_head_fwd_fused_kernel<20, 128, O2T, TIO>),       \
-                       dim3(grid2), dim3(kBlock), smem, stream,               \
-                       reinterpret_cast<const TIO*>(x.data_ptr()),            \
-                       W3f.data_ptr<float>(), b3f.data_ptr<float>(),          \
-                       W4f.data_ptr<float>(), b4f.data_ptr<float>(),          \
-                       reinterpret_cast<TIO*>(out.data_ptr()), B, O2, S);
-    if (bf16) {
-      if (O2 == 2) { PH_FWD_F(2, unsigned short) }
-      else { PH_FWD_F(1, unsigned short) }
-    } else {
-      if (O2 == 2) { PH_FWD_F(2, float) } else { PH_FWD_F(1, float) }
-    }
-#undef PH_FWD_F
-    DFNO_CHECK_LAUNCH("proj_head");
-    return out;
-  }
-  if (bf16) {
-    // bf16 activations, fp32 weights/math (host-casts the tiny weights)
-    auto W3f = W3.to(at::kFloat).contiguous();
-    auto b3f = b3.to(at::kFloat).contiguous();
-    auto W4f = W4.to(at::kFloat).contiguous();
-    auto b4f = b4.to(at::kFloat).contiguous();
-    auto inp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-    auto op = reinterpret_cast<unsigned short*>(out.data_ptr());
-#define PH_LAUNCH_BF(IM, OM, MTV, ITV)                                        \
-    hipLaunchKernelGGL((proj_head_fwd_kernel<float, IM, OM, 4, false, MTV,    \
-                                             ITV, unsigned short>),           \
-                       dim3(grid), dim3(kBlock), 0, stream, inp,              \
-                       W3f.data_ptr<float>(), b3f.data_ptr<float>(),          \
-                       W4f.data_ptr<float>(), b4f.data_ptr<float>(), op,      \
-                       B, I, M, O2, S);
-    if (I == 20 && M == 128 && O2 <= 2) { PH_LAUNCH_BF(24, 2, 128, 20) }
-    else if (I <= 24 && O2 <= 2) { PH_LAUNCH_BF(24, 2, 0, 0) }
-    else { PH_LAUNCH_BF(32, 8, 0, 0) }
-#undef PH_LAUNCH_BF
-    DFNO_CHECK_LAUNCH("proj_head");
-    return out;
-  }
-  check_real(W3, "W3"); check_real(b3, "b3");
-  check_real(W4, "W4"); check_real(b4, "b4");
-
-#define PH_LAUNCH_FT(V)                                                       \
-    hipLaunchKernelGGL((proj_head_fwd_kernel<scalar_t, IM, OM, 4, V, 128, 20>), \
-                       dim3(grid), dim3(kBlock), smem, stream,                \
-                       x.data_ptr<scalar_t>(), W3.data_ptr<scalar_t>(),       \
-                       b3.data_ptr<scalar_t>(), W4.data_ptr<scalar_t>(),      \
-                       b4.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),     \
-                       B, I, M, O2, S);
-#define PH_LAUNCH_F(V)                                                        \
-    hipLaunchKernelGGL((proj_head_fwd_kernel<scalar_t, IM, OM, 4, V>),        \
-                       dim3(grid), dim3(kBlock), smem, stream,                \
-                       x.data_ptr<scalar_t>(), W3.data_ptr<scalar_t>(),       \
-                       b3.data_ptr<scalar_t>(), W4.data_ptr<scalar_t>(),      \
-                       b4.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),     \
-                       B, I, M, O2, S);
-  AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "proj_head_fwd", [&] {
-    size_t smem = 0;
-    bool vec = vec_ok<scalar_t>(S, {x.data_ptr(), out.data_ptr()});
-    if (I == 20 && M == 128 && O2 <= 2) {
-      constexpr int IM = 24, OM = 2;   // flagship: fold M/I at compile time
-      if (vec) { PH_LAUNCH_FT(true) } else { PH_LAUNCH_FT(false) }
-    } else if (I <= 24 && O2 <= 2) {
-      constexpr int IM = 24, OM = 2;
-      if (vec) { PH_LAUNCH_F(true) } else { PH_LAUNCH_F(false) }
-    } else {
-      constexpr int IM = 32, OM = 8;
-      if (vec) { PH_LAUNCH_F(true) } else { PH_LAUNCH_F(false) }
-    }
-  });
-  DFNO_CHECK_LAUNCH("proj_head");
-#undef PH_LAUNCH_F
+  if (bf16)     // bf16 activations, fp32 weights and math
+    launch_proj_fwd<float, unsigned short>(d, x, f32(W3), f32(b3), f32(W4),
+                                           f32(b4), out);
+  else if (x.scalar_type() == at::kDouble)
+    launch_proj_fwd<double, double>(d, x, W3, b3, W4, b4, out);
+  else
+    launch_proj_fwd<float, float>(d, x, W3, b3, W4, b4, out);
   return out;
 }
 
 std::vector<at::Tensor> proj_head_bwd(const at::Tensor& gy, const at::Tensor& x,
                                       const at::Tensor& W3, const at::Tensor& b3,
                                       const at::Tensor& W4) {
-  check_real(gy, "gy"); check_real(x, "x"); check_real(W3, "W3");
-  check_real(b3, "b3"); check_real(W4, "W4");
-  int B = (int)x.size(0), I = (int)x.size(1);
-  long S = x.size(2);
-  int M = (int)W3.size(0), O2 = (int)W4.size(0);
-  TORCH_CHECK(I <= 32 && O2 <= 8 && M <= 512, "proj_head: unsupported dims");
-
-  auto gz3 = at::empty({B, M, S}, x.options());
-  auto gb3 = at::zeros({M}, x.options());
-  auto gW4 = at::zeros({O2, M}, x.options());
-  auto gb4 = at::zeros({O2}, x.options());
+  check_real(x, "x");
+  const ProjDims d = proj_dims(x, W3, b3, W4, gy, true);
+  TORCH_CHECK(d.bwd_lds(x.element_size()) <= kBwdLdsLimit,
+              "proj_head_bwd: LDS overflow");
+  auto gz3 = at::empty({d.B, d.M, d.S}, x.options());
+  auto gb3 = at::zeros({d.M}, x.options());
+  auto gW4 = at::zeros({d.O2, d.M}, x.options());
+  auto gb4 = at::zeros({d.O2}, x.options());
   if (x.numel() == 0) return {gz3, gb3, gW4, gb4};
-
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  int grid = launch_grid((long)B * ((S + 3) / 4), kBlock, 256L * 8);
-
-#define PH_LAUNCH_BT(V)                                                       \
-    hipLaunchKernelGGL((proj_head_bwd_kernel<scalar_t, IM, OM, 4, V, 128, 20>), \
-                       dim3(grid), dim3(kBlock), smem, stream,                \
-                       gy.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),       \
-                       W3.data_ptr<scalar_t>(), b3.data_ptr<scalar_t>(),      \
-                       W4.data_ptr<scalar_t>(), gz3.data_ptr<scalar_t>(),     \
-                       gb3.data_ptr<scalar_t>(),                              \
-                       gW4.data_ptr<scalar_t>(), gb4.data_ptr<scalar_t>(),    \
-                       B, I, M, O2, S);
-#define PH_LAUNCH_B(V)                                                        \
-    hipLaunchKernelGGL((proj_head_bwd_kernel<scalar_t, IM, OM, 4, V>),        \
-                       dim3(grid), dim3(kBlock), smem, stream,                \
-                       gy.data_ptr<scalar_t>(), x.data_ptr<scalar_t>(),       \
-                       W3.data_ptr<scalar_t>(), b3.data_ptr<scalar_t>(),      \
-                       W4.data_ptr<scalar_t>(), gz3.data_ptr<scalar_t>(),     \
-                       gb3.data_ptr<scalar_t>(),                              \
-                       gW4.data_ptr<scalar_t>(), gb4.data_ptr<scalar_t>(),    \
-                       B, I, M, O2, S);
-  AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "proj_head_bwd", [&] {
-    size_t smem = sizeof(scalar_t) *
-        ((size_t)M * I + M + (size_t)O2 * M + 4 * (size_t)M + 4 * (size_t)O2 * M);
-    TORCH_CHECK(smem <= 160 * 1024, "proj_head_bwd: LDS overflow");
-    bool vec = vec_ok<scalar_t>(S, {x.data_ptr(), gy.data_ptr(), gz3.data_ptr()});
-    if (I == 20 && M == 128 && O2 <= 2) {
-      constexpr int IM = 24, OM = 2;   // flagship fold
-      if (vec) { PH_LAUNCH_BT(true) } else { PH_LAUNCH_BT(false) }
-    } else if (I <= 24 && O2 <= 2) {
-      constexpr int IM = 24, OM = 2;
-      if (vec) { PH_LAUNCH_B(true) } else { PH_LAUNCH_B(false) }
-    } else {
-      constexpr int IM = 32, OM = 8;
-      if (vec) { PH_LAUNCH_B(true) } else { PH_LAUNCH_B(false) }
-    }
-  });
-  DFNO_CHECK_LAUNCH("proj_head");
-#undef PH_LAUNCH_B
+  if (x.scalar_type() == at::kDouble)
+    launch_proj_bwd<double>(d, gy, x, W3, b3, W4, gz3, gb3, gW4, gb4);
+  else
+    launch_proj_bwd<float>(d, gy, x, W3, b3, W4, gz3, gb3, gW4, gb4);
   return {gz3, gb3, gW4, gb4};
 }
 
@@ -872,53 +734,43 @@ std::vector<at::Tensor> proj_head_bwd_fused(const at::Tensor& gy,
                                             const at::Tensor& W3,
                                             const at::Tensor& b3,
                                             const at::Tensor& W4) {
+  const ProjDims d = proj_dims(x, W3, b3, W4, gy, true);
   const bool bf16 = x.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(gy.is_cuda() && gy.is_contiguous() && x.is_contiguous() &&
-              gy.scalar_type() == x.scalar_type(), "proj_head_bwd_fused IO");
-  int B = (int)x.size(0), I = (int)x.size(1);
-  long S = x.size(2);
-  int M = (int)W3.size(0), O2 = (int)W4.size(0);
-  TORCH_CHECK(I == 20 && M == 128 && O2 <= 2 &&
-              (bf16 || x.scalar_type() == at::kFloat),
+  TORCH_CHECK(d.pinned() && (bf16 || x.scalar_type() == at::kFloat),
               "proj_head_bwd_fused: flagship shape only");
-
-  auto W3f = bf16 ? W3.to(at::kFloat).contiguous() : W3;
-  auto b3f = bf16 ? b3.to(at::kFloat).contiguous() : b3;
-  auto W4f = bf16 ? W4.to(at::kFloat).contiguous() : W4;
-  check_real(W3f, "W3"); check_real(b3f, "b3"); check_real(W4f, "W4");
+  auto W3f = f32(W3), b3f = f32(b3), W4f = f32(W4);
   auto fopt = x.options().dtype(at::kFloat);   // weight grads accumulate fp32
-  auto gx = at::empty({B, I, S}, x.options());
-  auto gW3 = at::zeros({M, I}, fopt);
-  auto gb3 = at::zeros({M}, fopt);
-  auto gW4 = at::zeros({O2, M}, fopt);
-  auto gb4 = at::zeros({O2}, fopt);
+  auto gx = at::empty({d.B, d.I, d.S}, x.options());
+  auto gW3 = at::zeros({d.M, d.I}, fopt);
+  auto gb3 = at::zeros({d.M}, fopt);
+  auto gW4 = at::zeros({d.O2, d.M}, fopt);
+  auto gb4 = at::zeros({d.O2}, fopt);
   if (x.numel() == 0) return {gx, gW3, gb3, gW4, gb4};
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  constexpr int TS = 64, LD = TS + 4;
-  // gzt + xt + gyt + W3l + b3l + W4l + gb3s + gW4s (kernel layout order)
-  size_t smem = sizeof(float) *
-      ((size_t)128 * LD + 20 * LD + (size_t)O2 * TS + (size_t)128 * 20 +
-       128 + 2 * (size_t)O2 * 128 + 128);
-  long stiles = (S + TS - 1) / TS;
-  int grid = (int)std::min((long)B * stiles, 768L);
-#define PH_FUSED(O2T, TIO)                                                   \
-  hipLaunchKernelGGL((proj_head_bwd_fused_kernel<20, 128, O2T, TIO>),        \
-                     dim3(grid), dim3(kBlock), smem, stream,                 \
-                     reinterpret_cast<const TIO*>(gy.data_ptr()),            \
-                     reinterpret_cast<const TIO*>(x.data_ptr()),             \
-                     W3f.data_ptr<float>(), b3f.data_ptr<float>(),           \
-                     W4f.data_ptr<float>(),                                  \
-                     reinterpret_cast<TIO*>(gx.data_ptr()),                  \
-                     gW3.data_ptr<float>(), gb3.data_ptr<float>(),           \
-                     gW4.data_ptr<float>(), gb4.data_ptr<float>(),           \
-                     B, O2, S)
-  if (bf16) {
-    if (O2 == 2) PH_FUSED(2, unsigned short); else PH_FUSED(1, unsigned short);
-  } else {
-    if (O2 == 2) PH_FUSED(2, float); else PH_FUSED(1, float);
-  }
-#undef PH_FUSED
+  // 64-column tiles, grid-stride with at most 3 blocks per CU (by LDS)
+  const long stiles = (d.S + 63) / 64;
+  const int grid = (int)std::min((long)d.B * stiles, 768L);
+  auto go = [&](auto elem, auto o2t) {     // storage type by example, O2T
+    using TIO = decltype(elem);
+    constexpr int IT = 20, MT = 128, O2T = decltype(o2t)::value;
+    constexpr int TS = 64, LD = TS + 4;
+    // the kernel's layout order: gzt [MT][LD], xt [IT][LD], gyt [O2T][TS],
+    // W3l [MT*IT], b3l [MT], W4l [O2T*MT], gb3s [MT], gW4s [O2T*MT]
+    constexpr size_t smem = sizeof(float) *
+        (MT * LD + IT * LD + O2T * TS + MT * IT + MT + O2T * MT + MT + O2T * MT);
+    hipLaunchKernelGGL(
+        (proj_head_bwd_fused_kernel<IT, MT, O2T, TIO>), dim3(grid),
+        dim3(kBlock), smem, stream, static_cast<const TIO*>(gy.data_ptr()),
+        static_cast<const TIO*>(x.data_ptr()), W3f.data_ptr<float>(),
+        b3f.data_ptr<float>(), W4f.data_ptr<float>(),
+        static_cast<TIO*>(gx.data_ptr()), gW3.data_ptr<float>(),
+        gb3.data_ptr<float>(), gW4.data_ptr<float>(), gb4.data_ptr<float>(),
+        d.B, d.O2, d.S);
+  };
+  select_eq<1, 2>(d.O2, [&](auto o2t) {
+    if (bf16) go((unsigned short)0, o2t); else go(0.f, o2t);
+  });
   DFNO_CHECK_LAUNCH("proj_head_bwd_fused");
   return {gx, gW3, gb3, gW4, gb4};
 }

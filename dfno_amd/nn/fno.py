@@ -134,16 +134,8 @@ class DistributedFNONd(nn.Module):
         from ..dispatch import note_fallback
 
         l3, l4 = self.linear3, self.linear4
-        supported = (x.is_cuda and x.dtype in (torch.float32, torch.float64)
-                     and l3.in_features <= 32 and l3.out_features <= 512
-                     and l4.out_features <= 8)
-        # bf16: the fused pair (bf16-IO fwd + fused backward) covers the
-        # flagship head shape only
-        supported = supported or (
-            x.is_cuda and x.dtype == torch.bfloat16
-            and l3.in_features == 20 and l3.out_features == 128
-            and l4.out_features <= 2)
-        if supported:
+        if proj_head_supported(x, l3.in_features, l3.out_features,
+                               l4.out_features):
             with comm_region() as r:
                 W3 = l3.W_bcast(l3.W)
                 b3 = l3.b_bcast(l3.b)

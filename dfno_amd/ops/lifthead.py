@@ -17,6 +17,9 @@ __all__ = ["lift_head", "lift_head_supported"]
 # caps of the kernels (LDS tiles / register arrays are sized by them; the
 # extension re-checks every one before launching)
 MAX_T_IN, MAX_T_OUT, MAX_C_IN, MAX_WIDTH = 16, 64, 4, 24
+# T_in == 1 with T_out up to this goes in as [B, C, S] (kLaneKMaxTo in
+# csrc/lift_head.hip, which refuses a longer T_out in that form)
+LANE_K_MAX_T_OUT = 32
 
 
 def lift_head_supported(x, t_in, t_out, c_in, width) -> bool:
@@ -57,13 +60,13 @@ def lift_head(x, W1, b1, W2, b2):
     S = 1
     for d in sp:
         S *= d
-    if t_in == 1 and W1.shape[0] <= 32:
+    if t_in == 1 and W1.shape[0] <= LANE_K_MAX_T_OUT:
         # the T_in == 1 kernels take x with the unit time axis folded away
         xs = x.reshape(B, C, S).contiguous()
     else:
         xs = x.reshape(B, C, S, t_in).contiguous()
-        # the general kernels read the weights in x's dtype (no-op casts
-        # for a model built in one dtype)
-        W1, b1, W2, b2 = (t.to(x.dtype) for t in (W1, b1, W2, b2))
+    # the extension takes the weights in x's dtype (no-op casts for a model
+    # built in one dtype)
+    W1, b1, W2, b2 = (t.to(x.dtype) for t in (W1, b1, W2, b2))
     out = _LiftHeadFn.apply(xs, W1, b1.reshape(-1), W2, b2.reshape(-1))
     return out.reshape(B, W2.shape[0], *sp, W1.shape[0])

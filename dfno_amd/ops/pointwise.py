@@ -125,13 +125,36 @@ def _gelu_bwd(gy: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
     return gy * _gelu_grad(z)
 
 
+def mix_t_slab(dtype, O: int, I: int) -> int:
+    """Output rows per channel_mix_fwd_t call for gx = W^T gz with ``O`` gz
+    rows and ``I`` gx rows, or 0 for one call.  csrc/pointwise.hip streams
+    more than 32 input rows into register accumulators for up to 16 outputs
+    (32 in fp32) and otherwise stages a [rows x 32] tile plus W in at most
+    160 KiB of LDS; where that does not fit (fp64 512 -> 32 needs 262,400 B)
+    the outputs go in slabs of 16 through the accumulator kernel, which
+    streams at most 512 input rows."""
+    if dtype not in (torch.float32, torch.float64):
+        return 0
+    itemsize = 4 if dtype == torch.float32 else 8
+    acc_rows = 32 if dtype == torch.float32 else 16
+    if O <= 32 or I <= acc_rows or O > 512:
+        return 0
+    fits = itemsize * (O * 32 + I * O + I) <= 160 * 1024
+    return 0 if fits else 16
+
+
 def _mix_bwd_x(gz: torch.Tensor, W: torch.Tensor, op: str) -> torch.Tensor:
     """gx[b,i,s] = sum_o W[o,i] gz[b,o,s]."""
     O, I = W.shape
     if gz.is_cuda and _native_dt(gz):
         if min(I, O) > 32 and _wide_mix_ok(gz, O, I):
             return _wide_mix(gz, W, None, None, False, True, False)[0]
-        return _ext.get(required=True).channel_mix_fwd_t(gz, W)
+        ext = _ext.get(required=True)
+        slab = mix_t_slab(gz.dtype, O, I)
+        if slab:
+            return torch.cat([ext.channel_mix_fwd_t(gz, W[:, i:i + slab].contiguous())
+                              for i in range(0, I, slab)], dim=1)
+        return ext.channel_mix_fwd_t(gz, W)
     if _bf16_mix_ok(gz, O, I, op):
         gx, _ = _ext.get(required=True).bf16_channel_mix(
             gz.contiguous(), W.contiguous(), _ebf(gz.device), False, True,

@@ -333,6 +333,11 @@ def test_op_spectral_autograd_gpu():
     (2, 12, 64, 2, 1001),     # odd S (scalar path), multi-batch, O2=2
     (2, 20, 128, 2, 4099),    # fused backward: O2=2, tail tile, B=2
     (1, 20, 128, 1, 51233),   # fused backward: > 768 tiles (grid wrap) + tail
+    (2, 28, 40, 3, 1003),     # <32, 8> row, element-wise, across the batch
+    (1, 28, 40, 3, 1024),     # <32, 8> row, float4 IO in fp32
+    (1, 12, 64, 2, 1024),     # <24, 2> row, float4 IO in fp32
+    (1, 32, 128, 8, 260),     # I and O2 at their caps, one partial block;
+                              # backward LDS 39,424 B fp32 / 78,848 B fp64
 ])
 def test_proj_head(dtype, tt, B, I, M, O2, S):
     from dfno_amd.ops import proj_head
@@ -360,6 +365,29 @@ def test_proj_head(dtype, tt, B, I, M, O2, S):
     for a, b in [(x, xr), (W3, W3r), (b3, b3r), (W4, W4r), (b4, b4r)]:
         assert torch.allclose(a.grad, b.grad, rtol=tt * 30, atol=tt * 30), \
             f"grad max {(a.grad - b.grad).abs().max()}"
+
+
+def test_proj_head_entry_checks(ext):
+    """The extension refuses mismatched or out-of-range calls before any
+    launch."""
+    def args(dtype, B, I, M, O2, S):
+        dev = "cuda"
+        return [torch.randn(B, I, S, device=dev).to(dtype),
+                torch.randn(M, I, device=dev).to(dtype),
+                torch.randn(M, device=dev).to(dtype),
+                torch.randn(O2, M, device=dev).to(dtype),
+                torch.randn(O2, device=dev).to(dtype)]
+
+    x, W3, b3, W4, b4 = args(torch.float32, 1, 12, 64, 2, 256)
+    gy = torch.randn(1, 2, 252, device="cuda")            # wrong S
+    with pytest.raises(RuntimeError, match="gy must be"):
+        ext.proj_head_bwd(gy, x, W3, b3, W4)
+    W4bad = torch.randn(2, 65, device="cuda")             # W4.size(1) != M
+    with pytest.raises(RuntimeError, match="proj_head shapes"):
+        ext.proj_head_fwd(x, W3, b3, W4bad, b4)
+    with pytest.raises(RuntimeError, match="flagship shape only"):
+        ext.proj_head_fwd(*args(torch.bfloat16, 1, 12, 64, 1, 256))
+    torch.cuda.synchronize()
 
 
 # ---------------------------------------------------------------------------

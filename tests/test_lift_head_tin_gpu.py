@@ -104,6 +104,24 @@ def test_lift_tin1_wide_tout():
     _check(F32, B=1, C=2, S=50, Ti=1, To=48, W=20)
 
 
+# 7: the launch rows <LP, TIC, WT> that no case above lands on (LP 32 / 64
+#    lanes per point by To <= 32, TIC 4 / 16 by Ti <= 4, WT 20 at width 20,
+#    else 0); S = 45 is an odd point count over more than one block
+@pytest.mark.parametrize("dtype,Ti,To,W", [
+    (F32, 3, 20, 20),     # <32, 4, 20>
+    (F32, 12, 30, 20),    # <32, 16, 20>
+    (F32, 12, 30, 7),     # <32, 16, 0>
+    (BF16, 3, 20, 20),
+    (BF16, 12, 30, 20),
+    (BF16, 12, 30, 7),
+    (BF16, 4, 6, 12),     # <32, 4, 0>
+    (BF16, 3, 50, 9),     # <64, 4, 0>
+    (BF16, 3, 50, 20),    # <64, 4, 20>
+])
+def test_lift_launch_rows(dtype, Ti, To, W):
+    _check(dtype, B=1, C=2, S=45, Ti=Ti, To=To, W=W)
+
+
 def test_lift_gradcheck_fp64():
     from dfno_amd.ops import lift_head
     ts, _ = _inputs(F64, B=1, C=2, S=3, Ti=3, To=5, W=4)
@@ -132,6 +150,17 @@ def test_lift_gate():
         ext.lift_head_fwd(*ts)
     with pytest.raises(RuntimeError, match="unsupported dims"):
         ext.lift_head_bwd(gy, *ts)
+    # the [B,C,S] form (T_in == 1) goes through the same checks
+    ts, gy = _inputs(F32, B=1, C=2, S=4, Ti=1, To=8, W=4)
+    x3 = ts[0].reshape(1, 2, 4)
+    with pytest.raises(RuntimeError, match="gy shape"):
+        ext.lift_head_bwd(gy[..., :7].contiguous(), x3, *ts[1:])
+    W2bad = torch.randn(4, 3, device="cuda")              # W2.size(1) != C
+    with pytest.raises(RuntimeError, match="lift_head shapes"):
+        ext.lift_head_fwd(x3, ts[1], ts[2], W2bad, ts[4])
+    ts, gy = _inputs(F32, B=1, C=1, S=4, Ti=1, To=33, W=4)
+    with pytest.raises(RuntimeError, match="unsupported dims"):
+        ext.lift_head_fwd(ts[0].reshape(1, 1, 4), *ts[1:])
     torch.cuda.synchronize()
 
 

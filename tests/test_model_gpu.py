@@ -64,6 +64,49 @@ def test_fno_gpu_matches_reference_oracle_fp64():
         f"max {(y.cpu() - y_ref).abs().max()}"
 
 
+def test_projection_over_lds_bound_is_composed():
+    """A head inside the caps whose backward would need more LDS than the
+    fused kernel may ask for (fp64, 32 -> 512 -> 2: 192,512 B) takes the
+    composed path, recorded as a fallback, and matches the CPU model. The
+    grad-x of the composed linear3 (fp64 512 -> 32) runs in 16-row output
+    slabs (ops/pointwise.mix_t_slab)."""
+    from dfno_amd import dispatch
+    from dfno_amd.nn.linear import BroadcastedLinear
+    torch.manual_seed(3)
+    _, P_x, _ = dfno.create_standard_partitions((1, 1, 1, 1, 1))
+    in_shape = [1, 2, 6, 5, 3]
+    models = []
+    for dev in ("cpu", "cuda"):
+        m = dfno.DistributedFNONd(P_x, in_shape, 4, 32, (2, 2, 2), num_blocks=1,
+                                  device=torch.device(dev), dtype=torch.float64)
+        m.linear3 = BroadcastedLinear(P_x, 32, 512, dim=1,
+                                      device=torch.device(dev), dtype=torch.float64)
+        m.linear4 = BroadcastedLinear(P_x, 512, 2, dim=1,
+                                      device=torch.device(dev), dtype=torch.float64)
+        models.append(m)
+    cpu_model, gpu_model = models
+    gpu_model.load_state_dict({k: v.cuda() for k, v in cpu_model.state_dict().items()})
+
+    x = torch.rand(1, 32, 6, 5, 4, dtype=torch.float64)
+    xc = x.clone().requires_grad_(True)
+    xg = x.cuda().requires_grad_(True)
+    dispatch.reset_fallbacks()
+    y_cpu = cpu_model._projection(xc)
+    y_gpu = gpu_model._projection(xg)
+    assert y_gpu.shape == (1, 2, 6, 5, 4)
+    gy = torch.rand_like(y_cpu)
+    y_cpu.backward(gy)
+    y_gpu.backward(gy.cuda())
+    torch.cuda.synchronize()
+    assert any(op == "proj_head" for op, _ in dispatch.fallback_counts())
+    dispatch.reset_fallbacks()
+    assert torch.allclose(y_gpu.cpu(), y_cpu, rtol=1e-10, atol=1e-10)
+    assert torch.allclose(xg.grad.cpu(), xc.grad, rtol=1e-9, atol=1e-9)
+    for lc, lg in ((cpu_model.linear3, gpu_model.linear3),
+                   (cpu_model.linear4, gpu_model.linear4)):
+        assert torch.allclose(lg.W.grad.cpu(), lc.W.grad, rtol=1e-9, atol=1e-9)
+
+
 def test_native_extension_required_on_gpu():
     # the HIP extension must be importable on a GPU box — ops refuse to run
     # on CUDA tensors without it (no silent eager fallback)

@@ -67,3 +67,49 @@ def test_grad_w_caps():
     assert not grad_w_caps_ok(torch.bfloat16, 65, 128, 384)
     assert not grad_w_caps_ok(torch.bfloat16, 64, 129, 384)
     assert not grad_w_caps_ok(torch.bfloat16, 20, 20, 1000)
+
+
+def test_mix_t_slab():
+    """gx = W^T gz goes through channel_mix_fwd_t in one call wherever one of
+    its kernels takes the shape, and in 16-row output slabs where only the
+    LDS-staged one is left and its tile does not fit 160 KiB."""
+    from dfno_amd.ops.pointwise import mix_t_slab
+    f32, f64 = torch.float32, torch.float64
+    assert mix_t_slab(f64, 512, 32) == 16      # 8 * (512*32 + 32*512 + 32) B
+    assert mix_t_slab(f64, 128, 20) == 0       # 8 * (128*32 + 20*128 + 20) fits
+    assert mix_t_slab(f64, 512, 16) == 0       # accumulator kernel, one call
+    assert mix_t_slab(f64, 32, 512) == 0       # x-resident kernel
+    assert mix_t_slab(f32, 512, 32) == 0       # fp32 accumulators to 32 rows
+    assert mix_t_slab(f32, 20, 20) == 0
+    assert mix_t_slab(torch.bfloat16, 512, 32) == 0
+
+
+def test_proj_head_range():
+    """Support of the fused projection head as ops/projhead.py states it:
+    the caps I <= 32, M <= 512, O2 <= 8 and the LDS bound of the backward
+    (160 KiB) in fp32 / fp64, the pinned 20 -> 128 -> (<= 2) shape in bf16;
+    the one-kernel backward at the pinned shape in fp32 / bf16 only.
+    proj_head_supported is this plus x.is_cuda."""
+    from dfno_amd.ops.projhead import (proj_head_bwd_lds, proj_head_fused_bwd,
+                                       proj_head_range, proj_head_supported)
+    f32, f64, bf16 = torch.float32, torch.float64, torch.bfloat16
+    assert proj_head_range(f32, 20, 128, 1)
+    assert proj_head_bwd_lds(4, 32, 512, 8) == 157696
+    assert proj_head_range(f32, 32, 512, 8)
+    assert proj_head_bwd_lds(8, 20, 512, 1) == 122880
+    assert proj_head_range(f64, 20, 512, 1)
+    assert proj_head_bwd_lds(8, 32, 512, 2) == 192512
+    assert not proj_head_range(f64, 32, 512, 2)
+    assert not proj_head_range(f32, 33, 128, 1)
+    assert not proj_head_range(bf16, 12, 64, 1)
+    assert proj_head_range(bf16, 20, 128, 2)
+    assert not proj_head_range(torch.float16, 20, 128, 1)
+
+    assert proj_head_fused_bwd(f32, 20, 128, 1)
+    assert proj_head_fused_bwd(bf16, 20, 128, 2)
+    assert not proj_head_fused_bwd(f64, 20, 128, 1)
+    assert not proj_head_fused_bwd(f32, 12, 64, 1)
+    assert not proj_head_fused_bwd(f32, 20, 128, 3)
+
+    # host tensors never take the fused head
+    assert not proj_head_supported(torch.zeros(1), 20, 128, 1)
