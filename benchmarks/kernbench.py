@@ -180,26 +180,37 @@ def _alternate(fns, rounds=5, iters=50, all_rounds=False):
 
 
 def lift_bench():
-    """Fused lift head vs the composed linears at the Navier-Stokes shapes
-    ([10,1,X,X,10] -> 40, width 20): per-rank X = 32 and single-GPU X = 64.
-    Both paths run on identical inputs, alternating, in this one process."""
+    """Fused lift head vs the composed linears, on identical inputs,
+    alternating, in this one process.  Width 20: the Navier-Stokes shapes
+    ([10,1,X,X,10] -> 40), per-rank X = 32 and single-GPU X = 64.  Width 64
+    (the wide kernel rows): the flagship lift [1,2,64^3,1] -> 30 and the
+    Navier-Stokes lift [10,1,64,64,10] -> 40, with every round listed: the
+    fused route's slowest forward+backward round has to beat the composed
+    route's fastest."""
     from dfno_amd.ops import lift_head
     from dfno_amd.ops.pointwise import linear_nd
 
-    B, C, Ti, To, W = 10, 1, 10, 40, 20
-    for X in (32, 64):
-        S = X * X
+    cases = [  # (B, C, spatial, Ti, To, W, iters)
+        (10, 1, (32, 32), 10, 40, 20, 50),
+        (10, 1, (64, 64), 10, 40, 20, 50),
+        (1, 2, (64, 64, 64), 1, 30, 64, 10),
+        (10, 1, (64, 64), 10, 40, 64, 20),
+    ]
+    for B, C, sp, Ti, To, W, iters in cases:
+        S = 1
+        for d in sp:
+            S *= d
         for dtype in (torch.float32, torch.bfloat16):
             torch.manual_seed(0)
             es = 4 if dtype == torch.float32 else 2
-            x = torch.randn(B, C, X, X, Ti, device="cuda", dtype=dtype,
+            x = torch.randn(B, C, *sp, Ti, device="cuda", dtype=dtype,
                             requires_grad=True)
             ws = [torch.randn(To, Ti, device="cuda", dtype=dtype) / Ti,
                   torch.randn(To, device="cuda", dtype=dtype),
                   torch.randn(W, C, device="cuda", dtype=dtype) / C,
                   torch.randn(W, device="cuda", dtype=dtype)]
             ws = [w.requires_grad_(True) for w in ws]
-            gy = torch.randn(B, W, X, X, To, device="cuda", dtype=dtype)
+            gy = torch.randn(B, W, *sp, To, device="cuda", dtype=dtype)
 
             def fused():
                 return lift_head(x, *ws)
@@ -212,14 +223,26 @@ def lift_bench():
                 return lambda: torch.autograd.grad(f(), [x] + ws, gy)
 
             with torch.no_grad():
-                tf, tc = _alternate([fused, composed])
-            tfb, tcb = _alternate([fb(fused), fb(composed)])
+                rf, rc = _alternate([fused, composed], iters=iters,
+                                    all_rounds=True)
+            rfb, rcb = _alternate([fb(fused), fb(composed)], iters=iters,
+                                  all_rounds=True)
+            tf, tc, tfb, tcb = (sorted(r)[len(r) // 2]
+                                for r in (rf, rc, rfb, rcb))
             nin, nout = B * C * S * Ti, B * W * S * To
-            tag = f"S={X}x{X} {str(dtype).split('.')[-1]}"
+            tag = (f"W={W} S={'x'.join(str(d) for d in sp)} "
+                   f"{str(dtype).split('.')[-1]}")
             report(f"lift fused    fwd      {tag}", tf, (nin + nout) * es)
             report(f"lift composed fwd      {tag}", tc, (nin + nout) * es)
             report(f"lift fused    fwd+bwd  {tag}", tfb, 2 * (nin + nout) * es + nin * es)
             report(f"lift composed fwd+bwd  {tag}", tcb, 2 * (nin + nout) * es + nin * es)
+            if W > 24:
+                ms = lambda r: [round(t * 1e3, 3) for t in r]  # noqa: E731
+                print(f"  fwd rounds ms: fused {ms(rf)}  composed {ms(rc)}")
+                print(f"  fwd+bwd rounds ms: fused {ms(rfb)}  composed "
+                      f"{ms(rcb)}  slowest fused < fastest composed: "
+                      f"{max(rfb) < min(rcb)}")
+            del x, gy
 
 
 def lift_model_bench():
@@ -228,7 +251,7 @@ def lift_model_bench():
     import dfno_amd as dfno
     import dfno_amd.ops as ops
 
-    gate = ops.lift_head_supported
+    gate, wide_gate = ops.lift_head_supported, ops.lift_head_wide_range
     for dtype in (torch.float32, torch.bfloat16):
         torch.manual_seed(0)
         _, P_x, _ = dfno.create_standard_partitions((1, 1, 1, 1, 1))
@@ -239,12 +262,15 @@ def lift_model_bench():
 
         def step(on):
             def run():
-                ops.lift_head_supported = gate if on else (lambda *a: False)
+                off = lambda *a: False  # noqa: E731
+                ops.lift_head_supported = gate if on else off
+                ops.lift_head_wide_range = wide_gate if on else off
                 try:
                     model.zero_grad(set_to_none=True)
                     model(x).float().square().mean().backward()
                 finally:
                     ops.lift_head_supported = gate
+                    ops.lift_head_wide_range = wide_gate
             return run
 
         import warnings

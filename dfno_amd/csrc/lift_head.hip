@@ -36,20 +36,39 @@ using namespace dfno_io;
 
 constexpr int kBlock = 256;
 
+// Width rows.  WCAP is the width cap that sizes the W2 / b2 LDS arrays: 24
+// for the narrow row, 64 for widths 25..64.  The backward kernels walk the
+// width in WCAP / SR slabs of SR rows: one 24-row slab in the narrow row, two
+// 32-row slabs in the wide one, each slab with its own gy preload, its own
+// fill of the per-wave gz tile and its own two 16-row MFMA m-tiles, so the
+// tile and the preload stay near the narrow row's size at width 64.
+template <int WCAP> struct LiftSlab {
+  static_assert(WCAP == 24 || WCAP == 64, "width rows: 24 or 64");
+  static constexpr int SR = WCAP > 32 ? 32 : WCAP;   // rows per slab
+  static constexpr int NSLAB = WCAP / SR;
+  static constexpr int NMT = 2 * NSLAB;              // 16-row MFMA m-tiles
+};
+
+// orders a wave's accesses to its private LDS tiles (no s_barrier)
+__device__ __forceinline__ void lh_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // fp32 lane-per-k variants: each 64-lane wave covers TWO s-points with
 // lanes 0..Tn-1 / 32..32+Tn-1 owning one time column each, so every gy
 // read and out write is a contiguous Tn-dword run (a one-point-per-thread
 // layout streams 30-float runs per lane -> fully scattered wave accesses;
 // measured 699/843 us vs ~110/130 us of traffic).  Per-lane state is
 // ~40 VGPRs; gW1/gb1 partials accumulate in registers (k fixed per lane).
-template <int WT, typename TIO = float>
+template <int WT, int WCAP, typename TIO = float>
 __global__ __launch_bounds__(kBlock) void lift_head_fwd_lk_kernel(
     const TIO* __restrict__ x, const float* __restrict__ W1,
     const float* __restrict__ b1, const float* __restrict__ W2,
     const float* __restrict__ b2, TIO* __restrict__ out,
     int B, int C, int W, int Tn, long S) {
   constexpr int CC = 4;
-  __shared__ float w1[32], bb1[32], w2[24 * CC], bb2[24];
+  __shared__ float w1[32], bb1[32], w2[WCAP * CC], bb2[WCAP];
   for (int k = threadIdx.x; k < Tn; k += kBlock) { w1[k] = W1[k]; bb1[k] = b1[k]; }
   for (int k = threadIdx.x; k < W * C; k += kBlock) w2[k] = W2[k];
   for (int k = threadIdx.x; k < W; k += kBlock) bb2[k] = b2[k];
@@ -89,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_lk_kernel(
   }
 }
 
-template <int WT, typename TIO = float>
+template <int WT, int WCAP, typename TIO = float>
 __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
     const TIO* __restrict__ gy, const TIO* __restrict__ x,
     const float* __restrict__ W1, const float* __restrict__ b1,
@@ -99,13 +118,17 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
     int B, int C, int W, int Tn, long S) {
   constexpr int CC = 4;
   constexpr int GLD = 68;                     // gz/h tile row pad (banks)
-  __shared__ float w1[32], bb1[32], w2[24 * CC], bb2[24];
-  // per-wave tiles: gz [24 w][64 lanes] and h [4 c][64 lanes]; the gW2 and
+  constexpr int SR = LiftSlab<WCAP>::SR, NSLAB = LiftSlab<WCAP>::NSLAB;
+  constexpr int NMT = LiftSlab<WCAP>::NMT;
+  // row-loop trip bound: the pin, a slab, or (one slab) "until w == W"
+  constexpr int WL = WT > 0 ? WT : (NSLAB > 1 ? SR : 512);
+  __shared__ float w1[32], bb1[32], w2[WCAP * CC], bb2[WCAP];
+  // per-wave tiles: gz [SR w][64 lanes] and h [4 c][64 lanes]; the gW2 and
   // gb2 reductions run as v_mfma_f32_16x16x4 over these (B-operand column
   // 4 is a constant ones column giving gb2) with the C fragments carried
   // in registers across pairs — the per-pair 6-shuffle wave_sum chains of
   // the first cut were the whole kernel's latency.
-  __shared__ float gzt[4][24 * GLD];
+  __shared__ float gzt[4][SR * GLD];
   __shared__ float ht[4][CC * GLD];
   for (int k = threadIdx.x; k < Tn; k += kBlock) { w1[k] = W1[k]; bb1[k] = b1[k]; }
   for (int k = threadIdx.x; k < W * C; k += kBlock) w2[k] = W2[k];
@@ -120,9 +143,9 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
   const int l16 = lane & 15;
   const int kg = lane >> 4;
   float pgW1 = 0.f, pgb1 = 0.f;               // per-lane: k is fixed
-  f32x4 wacc[2];                           // gW2/gb2 frags (2 m-tiles)
-  wacc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-  wacc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 wacc[NMT];                         // gW2/gb2 frags (2 m-tiles a slab)
+#pragma unroll
+  for (int mt = 0; mt < NMT; ++mt) wacc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float* gzw = &gzt[wave][0];
   float* hw = &ht[wave][0];
 
@@ -145,41 +168,53 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
         hw[c * GLD + lane] = h[c];
       }
     }
-    // all W gy columns preloaded back-to-back: one memory round trip per
-    // pair instead of one per unroll batch (the loads were the kernel's
+    // per slab of SR rows (gh accumulates over the slabs): all of the slab's
+    // gy columns preloaded back-to-back, one memory round trip per pair and
+    // slab instead of one per unroll batch (the loads were the kernel's
     // whole latency — all reduction variants measured the same ~900 us)
-    float gyv[WT > 0 ? WT : 24];
 #pragma unroll
-    for (int w = 0; w < (WT > 0 ? WT : 24); ++w) {
-      gyv[w] = (w < W && ev && kv)
-                   ? ld(gy + ((b * W + w) * S + s) * Tn + k) : 0.f;
-    }
+    for (int sl = 0; sl < NSLAB; ++sl) {
+      const int w0 = sl * SR;                 // wave-uniform
+      if (NSLAB > 1 && w0 >= W) break;
+      float gyv[WT > 0 ? WT : SR];
+#pragma unroll
+      for (int wl = 0; wl < (WT > 0 ? WT : SR); ++wl) {
+        const int w = w0 + wl;
+        gyv[wl] = (w < W && ev && kv)
+                      ? ld(gy + ((b * W + w) * S + s) * Tn + k) : 0.f;
+      }
+      // the previous slab's MFMA reads of the gz tile come first
+      if (NSLAB > 1) lh_wave_sync();
 #pragma unroll 4
-    for (int w = 0; w < (WT > 0 ? WT : 512); ++w) {
-      if (WT == 0 && w >= W) break;
-      float z2 = bb2[w];
+      for (int wl = 0; wl < WL; ++wl) {
+        const int w = w0 + wl;
+        if (WT == 0 && w >= W) break;
+        float z2 = bb2[w];
 #pragma unroll
-      for (int c = 0; c < CC; ++c)
-        if (c < C) z2 += w2[w * C + c] * h[c];
-      const float gz2 = gyv[w] * dfno_gelu::gelu_grad(z2);
-      gzw[w * GLD + lane] = gz2;
+        for (int c = 0; c < CC; ++c)
+          if (c < C) z2 += w2[w * C + c] * h[c];
+        const float gz2 = gyv[wl] * dfno_gelu::gelu_grad(z2);
+        gzw[wl * GLD + lane] = gz2;
 #pragma unroll
-      for (int c = 0; c < CC; ++c)
-        if (c < C) gh[c] += w2[w * C + c] * gz2;
-    }
-    // gW2/gb2 fragment update from this pair's tiles (wave-synchronous:
-    // same wave wrote gzt/ht just above)
+        for (int c = 0; c < CC; ++c)
+          if (c < C) gh[c] += w2[w * C + c] * gz2;
+      }
+      if (NSLAB > 1) lh_wave_sync();
+      // gW2/gb2 fragment update from this slab's tiles (wave-synchronous:
+      // same wave wrote gzt/ht just above)
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const int wrow = mt * 16 + l16;
-      const bool av = wrow < W;
+      for (int mt = 0; mt < 2; ++mt) {
+        if (NSLAB > 1 && w0 + mt * 16 >= W) break;
+        const int wrow = w0 + mt * 16 + l16;
+        const bool av = wrow < W;
 #pragma unroll 4
-      for (int k0 = 0; k0 < 64; k0 += 4) {
-        const float a = av ? gzw[wrow * GLD + k0 + kg] : 0.f;
-        const float bb = (l16 < C) ? hw[l16 * GLD + k0 + kg]
-                                   : (l16 == C ? 1.f : 0.f);
-        wacc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, wacc[mt],
-                                                        0, 0, 0);
+        for (int k0 = 0; k0 < 64; k0 += 4) {
+          const float a = av ? gzw[(mt * 16 + l16) * GLD + k0 + kg] : 0.f;
+          const float bb = (l16 < C) ? hw[l16 * GLD + k0 + kg]
+                                     : (l16 == C ? 1.f : 0.f);
+          wacc[2 * sl + mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+              a, bb, wacc[2 * sl + mt], 0, 0, 0);
+        }
       }
     }
     // gz1 = gh * gelu'(z1); per-lane gW1/gb1 partials; gx via 32-lane
@@ -208,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
     atomicAdd(&gb1[k], pgb1);
   }
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
+  for (int mt = 0; mt < NMT; ++mt) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int w = mt * 16 + kg * 4 + r;
@@ -234,12 +269,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_lk_kernel(
 // Rows are zero-padded to the TIC cap so the dot product has no guards.
 // The tiles are wave-private: ordering is by lh_wave_sync(), no s_barrier.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void lh_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-template <int LP, int TIC, int WT, typename TIO>
+template <int LP, int TIC, int WT, int WCAP, typename TIO>
 __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
     const TIO* __restrict__ x, const TIO* __restrict__ W1,
     const TIO* __restrict__ b1, const TIO* __restrict__ W2,
@@ -249,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
   constexpr int PW = 64 / LP;                 // points per wave
   constexpr int XT = PW * CC * TIC;           // x tile floats per wave
   constexpr int NPASS = (XT + 63) / 64;
-  __shared__ float w2[24 * CC], bb2[24];
+  __shared__ float w2[WCAP * CC], bb2[WCAP];
   __shared__ float xt[kBlock / 64][XT];
   for (int j = threadIdx.x; j < W * C; j += kBlock) w2[j] = ld(W2 + j);
   for (int j = threadIdx.x; j < W; j += kBlock) bb2[j] = ld(b2 + j);
@@ -343,7 +373,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_kernel(
 // of the block's waves are summed in LDS before the global atomics: the
 // destinations are one ~2 KB row shared by every block, where contended
 // float atomics are an order of magnitude slower than streaming ones.
-template <int LP, int TIC, int WT, typename TIO>
+template <int LP, int TIC, int WT, int WCAP, typename TIO>
 __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
     const TIO* __restrict__ gy, const TIO* __restrict__ x,
     const TIO* __restrict__ W1, const TIO* __restrict__ b1,
@@ -357,8 +387,12 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
   constexpr int XT = PW * CC * TIC;
   constexpr int NPASS = (XT + 63) / 64;
   constexpr int NW = kBlock / 64;
-  __shared__ float w1s[64 * 16], w2[24 * CC], bb2[24];
-  __shared__ float gzt[NW][24 * GLD];
+  constexpr int SR = LiftSlab<WCAP>::SR, NSLAB = LiftSlab<WCAP>::NSLAB;
+  constexpr int NMT = LiftSlab<WCAP>::NMT;
+  // row-loop trip bound: the pin, a slab, or (one slab) "until w == W"
+  constexpr int WL = WT > 0 ? WT : (NSLAB > 1 ? SR : 512);
+  __shared__ float w1s[64 * 16], w2[WCAP * CC], bb2[WCAP];
+  __shared__ float gzt[NW][SR * GLD];
   __shared__ float ht[NW][CC * GLD];
   __shared__ float xt[NW][XT];
   for (int j = threadIdx.x; j < To * Ti; j += kBlock) w1s[j] = ld(W1 + j);
@@ -386,9 +420,9 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
   }
   const float b1k = kv ? ld(b1 + k) : 0.f;
   float pgb1 = 0.f;
-  f32x4 wacc[2];                           // gW2/gb2 frags (2 m-tiles)
-  wacc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-  wacc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 wacc[NMT];                         // gW2/gb2 frags (2 m-tiles a slab)
+#pragma unroll
+  for (int mt = 0; mt < NMT; ++mt) wacc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
   // one point per wave: lanes >= To hold zeros, skip their MFMA k-steps
   const int kend = (PW == 1) ? ((To + 3) & ~3) : 64;
 
@@ -439,53 +473,67 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
     const bool ev = e < N;
     const int b = e / S;
     const int s = e - b * S;
-    // all W gy columns preloaded back-to-back: one memory round trip
-    float gyv[WT > 0 ? WT : 24];
-#pragma unroll
-    for (int w = 0; w < (WT > 0 ? WT : 24); ++w) {
-      gyv[w] = (w < W && ev && kv)
-                   ? ld(gy + ((long)(b * W + w) * S + s) * To + k) : 0.f;
-    }
     float z1[CC], h[CC], gh[CC];
+    // per slab of SR rows; gh accumulates over the slabs
 #pragma unroll
-    for (int c = 0; c < CC; ++c) {
-      if (c < C) {
-        float z = b1k;
+    for (int sl = 0; sl < NSLAB; ++sl) {
+      const int w0 = sl * SR;                 // wave-uniform
+      if (sl > 0 && w0 >= W) break;
+      // the slab's gy columns preloaded back-to-back: one memory round trip
+      float gyv[WT > 0 ? WT : SR];
 #pragma unroll
-        for (int i = 0; i < TIC; ++i) z += w1r[i] * xw[(p * CC + c) * TIC + i];
-        z1[c] = z;
-        h[c] = kv ? dfno_gelu::gelu(z) : 0.f;
-        gh[c] = 0.f;
-        hw[c * GLD + lane] = h[c];
+      for (int wl = 0; wl < (WT > 0 ? WT : SR); ++wl) {
+        const int w = w0 + wl;
+        gyv[wl] = (w < W && ev && kv)
+                      ? ld(gy + ((long)(b * W + w) * S + s) * To + k) : 0.f;
       }
-    }
+      if (sl == 0) {
+        // z1 / h of the point, under the first slab's loads
+#pragma unroll
+        for (int c = 0; c < CC; ++c) {
+          if (c < C) {
+            float z = b1k;
+#pragma unroll
+            for (int i = 0; i < TIC; ++i)
+              z += w1r[i] * xw[(p * CC + c) * TIC + i];
+            z1[c] = z;
+            h[c] = kv ? dfno_gelu::gelu(z) : 0.f;
+            gh[c] = 0.f;
+            hw[c * GLD + lane] = h[c];
+          }
+        }
+      } else {
+        lh_wave_sync();                       // gz tile free: MFMA reads done
+      }
 #pragma unroll 4
-    for (int w = 0; w < (WT > 0 ? WT : 512); ++w) {
-      if (WT == 0 && w >= W) break;
-      float z2 = bb2[w];
+      for (int wl = 0; wl < WL; ++wl) {
+        const int w = w0 + wl;
+        if (WT == 0 && w >= W) break;
+        float z2 = bb2[w];
 #pragma unroll
-      for (int c = 0; c < CC; ++c)
-        if (c < C) z2 += w2[w * C + c] * h[c];
-      const float gz2 = gyv[w] * dfno_gelu::gelu_grad(z2);
-      gzw[w * GLD + lane] = gz2;
+        for (int c = 0; c < CC; ++c)
+          if (c < C) z2 += w2[w * C + c] * h[c];
+        const float gz2 = gyv[wl] * dfno_gelu::gelu_grad(z2);
+        gzw[wl * GLD + lane] = gz2;
 #pragma unroll
-      for (int c = 0; c < CC; ++c)
-        if (c < C) gh[c] += w2[w * C + c] * gz2;
-    }
-    lh_wave_sync();
-    // gW2/gb2 fragment update from this iteration's tiles
+        for (int c = 0; c < CC; ++c)
+          if (c < C) gh[c] += w2[w * C + c] * gz2;
+      }
+      lh_wave_sync();
+      // gW2/gb2 fragment update from this slab's tiles
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      if (mt * 16 < W) {
-        const int wrow = mt * 16 + l16;
-        const bool av = wrow < W;
+      for (int mt = 0; mt < 2; ++mt) {
+        if (w0 + mt * 16 < W) {
+          const int wrow = w0 + mt * 16 + l16;
+          const bool av = wrow < W;
 #pragma unroll 4
-        for (int k0 = 0; k0 < kend; k0 += 4) {
-          const float a = av ? gzw[wrow * GLD + k0 + kg] : 0.f;
-          const float bb = (l16 < C) ? hw[l16 * GLD + k0 + kg]
-                                     : (l16 == C ? 1.f : 0.f);
-          wacc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, wacc[mt],
-                                                          0, 0, 0);
+          for (int k0 = 0; k0 < kend; k0 += 4) {
+            const float a = av ? gzw[(mt * 16 + l16) * GLD + k0 + kg] : 0.f;
+            const float bb = (l16 < C) ? hw[l16 * GLD + k0 + kg]
+                                       : (l16 == C ? 1.f : 0.f);
+            wacc[2 * sl + mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                a, bb, wacc[2 * sl + mt], 0, 0, 0);
+          }
         }
       }
     }
@@ -529,10 +577,10 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
   float* red = &gzt[0][0];
   float* r_gW1 = red;                         // [To*Ti] <= 1024
   float* r_gb1 = red + 64 * 16;               // [To]    <= 64
-  float* r_gW2 = r_gb1 + 64;                  // [W*C]   <= 96
-  float* r_gb2 = r_gW2 + 24 * CC;             // [W]     <= 24
-  static_assert(64 * 16 + 64 + 24 * CC + 24 <= NW * 24 * GLD, "flush tile");
-  for (int j = threadIdx.x; j < 64 * 16 + 64 + 24 * CC + 24; j += kBlock)
+  float* r_gW2 = r_gb1 + 64;                  // [W*C]   <= WCAP * 4
+  float* r_gb2 = r_gW2 + WCAP * CC;           // [W]     <= WCAP
+  static_assert(64 * 16 + 64 + WCAP * CC + WCAP <= NW * SR * GLD, "flush tile");
+  for (int j = threadIdx.x; j < 64 * 16 + 64 + WCAP * CC + WCAP; j += kBlock)
     red[j] = 0.f;
   __syncthreads();
   if (kv) {
@@ -542,7 +590,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
     atomicAdd(&r_gb1[k], pgb1);
   }
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
+  for (int mt = 0; mt < NMT; ++mt) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int w = mt * 16 + kg * 4 + r;
@@ -568,13 +616,13 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_kernel(
 // included: one thread per point, the time axis walked KC columns at a time
 // so that the h tile [C][KC] stays in registers; x is re-read through L1
 // instead of living in registers.
-template <typename T>
+template <typename T, int WCAP>
 __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_chunk_kernel(
     const T* __restrict__ x, const T* __restrict__ W1, const T* __restrict__ b1,
     const T* __restrict__ W2, const T* __restrict__ b2, T* __restrict__ out,
     int C, int W, int Ti, int To, int S, int N) {
   constexpr int CC = 4, KC = 8;
-  __shared__ T w1[64 * 16], bb1[64], w2[24 * CC], bb2[24];
+  __shared__ T w1[64 * 16], bb1[64], w2[WCAP * CC], bb2[WCAP];
   for (int j = threadIdx.x; j < To * Ti; j += kBlock) w1[j] = W1[j];
   for (int j = threadIdx.x; j < To; j += kBlock) bb1[j] = b1[j];
   for (int j = threadIdx.x; j < W * C; j += kBlock) w2[j] = W2[j];
@@ -619,7 +667,7 @@ __global__ __launch_bounds__(kBlock) void lift_head_fwd_gen_chunk_kernel(
   }
 }
 
-template <typename T>
+template <typename T, int WCAP>
 __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
     const T* __restrict__ gy, const T* __restrict__ x,
     const T* __restrict__ W1, const T* __restrict__ b1,
@@ -628,9 +676,10 @@ __global__ __launch_bounds__(kBlock) void lift_head_bwd_gen_chunk_kernel(
     T* __restrict__ gW2, T* __restrict__ gb2,
     int C, int W, int Ti, int To, int S, int N) {
   constexpr int CC = 4, KC = 8;
-  __shared__ T w1[64 * 16], bb1[64], w2[24 * CC], bb2[24];
+  __shared__ T w1[64 * 16], bb1[64], w2[WCAP * CC], bb2[WCAP];
   // block accumulators (lane 0 of each wave adds its wave's sum)
-  __shared__ T a_gW1[64 * 16], a_gb1[64], a_gW2[24 * CC], a_gb2[24];
+  __shared__ T a_gW1[64 * 16], a_gb1[64], a_gW2[WCAP * CC],
+      a_gb2[WCAP];
   for (int j = threadIdx.x; j < To * Ti; j += kBlock) { w1[j] = W1[j]; a_gW1[j] = T(0); }
   for (int j = threadIdx.x; j < To; j += kBlock) { bb1[j] = b1[j]; a_gb1[j] = T(0); }
   for (int j = threadIdx.x; j < W * C; j += kBlock) { w2[j] = W2[j]; a_gW2[j] = T(0); }
@@ -779,8 +828,8 @@ LiftDims lift_dims(const at::Tensor& x, const at::Tensor& W1,
   TORCH_CHECK(W1.size(1) == Ti && W2.size(1) == C && b1.size(0) == To &&
               b2.size(0) == W, "lift_head shapes");
   TORCH_CHECK(C >= 1 && C <= 4 && Ti >= 1 && Ti <= 16 && To >= 1 && To <= 64 &&
-              W >= 1 && W <= 24, "lift_head: unsupported dims (C <= 4, "
-              "T_in <= 16, T_out <= 64, width <= 24)");
+              W >= 1 && W <= 64, "lift_head: unsupported dims (C <= 4, "
+              "T_in <= 16, T_out <= 64, width <= 64)");
   TORCH_CHECK(x.dim() == 4 || To <= kLaneKMaxTo,
               "lift_head: unsupported dims ([B,C,S] takes T_out <= 32)");
   TORCH_CHECK(B * S < (1L << 30), "lift_head: too many grid points");
@@ -810,12 +859,15 @@ struct LiftCall {
 };
 
 // Rows (fp32 and bf16 each; TIO is the storage type of x / out / gy / gx):
-//   [B,C,S]       lane-per-k    <WT>            WT 20 at width 20, else 0
-//   [B,C,S,Ti]    general       <LP, TIC, WT>   LP 32 lanes per point at
-//                 T_out <= 32, else 64; TIC 4 x steps in registers at
-//                 T_in <= 4, else 16; WT as above
-//   fp64          chunk kernels, both forms, no template rows
-// Grids are blocks of 4 waves, grid-stride: lane-per-k one wave per pair of
+//   [B,C,S]       lane-per-k    <WT, WCAP>      WT 20 at width 20, else 0;
+//                 WCAP 24 at width <= 24, else 64 (LiftSlab: the backward
+//                 walks two 32-row slabs, four MFMA fragments)
+//   [B,C,S,Ti]    general       <LP, TIC, WT, WCAP>   LP 32 lanes per point
+//                 at T_out <= 32, else 64; TIC 4 x steps in registers at
+//                 T_in <= 4, else 16; WT and WCAP as above
+//   fp64          chunk kernels, both forms     <WCAP> as above
+// The width rows are <20, 24>, <0, 24> and <0, 64>: no width above 24 is
+// pinned.  Grids are blocks of 4 waves, grid-stride: lane-per-k one wave per pair of
 // points, forward and backward at most 8 blocks per CU; general one wave per
 // 64 / LP points, forward at most 8 per CU, backward 3 (one resident round:
 // 3 fit by VGPRs at the T_in cap, and every block ends with its weight-grad
@@ -823,15 +875,19 @@ struct LiftCall {
 // point, at most 8 per CU.
 template <typename F>
 void with_width(const LiftDims& d, F&& f) {
-  select_bool(d.W == 20, [&](auto pin) {
-    f(int_c<decltype(pin)::value ? 20 : 0>{});
-  });
+  if (d.W > 24) {
+    f(int_c<0>{}, int_c<64>{});
+  } else {
+    select_bool(d.W == 20, [&](auto pin) {
+      f(int_c<decltype(pin)::value ? 20 : 0>{}, int_c<24>{});
+    });
+  }
 }
 template <typename F>
 void with_lift_row(const LiftDims& d, F&& f) {
   select_le<32, 64>(d.To, [&](auto lp) {
     select_le<4, 16>(d.Ti, [&](auto tic) {
-      with_width(d, [&](auto wt) { f(lp, tic, wt); });
+      with_width(d, [&](auto wt, auto wcap) { f(lp, tic, wt, wcap); });
     });
   });
 }
@@ -851,17 +907,17 @@ void launch_lift_lk(const LiftCall& c) {
   const auto W1f = f32(c.W1), b1f = f32(c.b1), W2f = f32(c.W2), b2f = f32(c.b2);
   const int grid =
       launch_grid(2 * (((long)d.N + 1) / 2) * 32, kBlock, 256L * 8);
-  with_width(d, [&](auto wt) {
-    constexpr int WT = decltype(wt)::value;
+  with_width(d, [&](auto wt, auto wcap) {
+    constexpr int WT = decltype(wt)::value, WCAP = decltype(wcap)::value;
     if (c.gy == nullptr) {
-      hipLaunchKernelGGL((lift_head_fwd_lk_kernel<WT, TIO>), dim3(grid),
+      hipLaunchKernelGGL((lift_head_fwd_lk_kernel<WT, WCAP, TIO>), dim3(grid),
                          dim3(kBlock), 0, c.stream, lift_in<TIO>(c.x),
                          W1f.data_ptr<float>(), b1f.data_ptr<float>(),
                          W2f.data_ptr<float>(), b2f.data_ptr<float>(),
                          static_cast<TIO*>(c.out->data_ptr()), d.B, d.C, d.W,
                          d.To, (long)d.S);
     } else {
-      hipLaunchKernelGGL((lift_head_bwd_lk_kernel<WT, TIO>), dim3(grid),
+      hipLaunchKernelGGL((lift_head_bwd_lk_kernel<WT, WCAP, TIO>), dim3(grid),
                          dim3(kBlock), 0, c.stream, lift_in<TIO>(*c.gy),
                          lift_in<TIO>(c.x), W1f.data_ptr<float>(),
                          b1f.data_ptr<float>(), W2f.data_ptr<float>(),
@@ -878,12 +934,12 @@ void launch_lift_lk(const LiftCall& c) {
 template <typename TIO>
 void launch_lift_gen(const LiftCall& c) {
   const LiftDims& d = c.d;
-  with_lift_row(d, [&](auto lp, auto tic, auto wt) {
+  with_lift_row(d, [&](auto lp, auto tic, auto wt, auto wcap) {
     constexpr int LP = decltype(lp)::value, TIC = decltype(tic)::value;
-    constexpr int WT = decltype(wt)::value;
+    constexpr int WT = decltype(wt)::value, WCAP = decltype(wcap)::value;
     const long nwork = (d.N + 64 / LP - 1) / (64 / LP);
     if (c.gy == nullptr) {
-      hipLaunchKernelGGL((lift_head_fwd_gen_kernel<LP, TIC, WT, TIO>),
+      hipLaunchKernelGGL((lift_head_fwd_gen_kernel<LP, TIC, WT, WCAP, TIO>),
                          dim3(launch_grid(nwork, kBlock / 64, 256L * 8)),
                          dim3(kBlock), 0, c.stream, lift_in<TIO>(c.x),
                          lift_in<TIO>(c.W1), lift_in<TIO>(c.b1),
@@ -891,7 +947,7 @@ void launch_lift_gen(const LiftCall& c) {
                          static_cast<TIO*>(c.out->data_ptr()), d.C, d.W, d.Ti,
                          d.To, d.S, d.N);
     } else {
-      hipLaunchKernelGGL((lift_head_bwd_gen_kernel<LP, TIC, WT, TIO>),
+      hipLaunchKernelGGL((lift_head_bwd_gen_kernel<LP, TIC, WT, WCAP, TIO>),
                          dim3(launch_grid(nwork, kBlock / 64, 256L * 3)),
                          dim3(kBlock), 0, c.stream, lift_in<TIO>(*c.gy),
                          lift_in<TIO>(c.x), lift_in<TIO>(c.W1),
@@ -907,22 +963,26 @@ void launch_lift_gen(const LiftCall& c) {
 void launch_lift_chunk(const LiftCall& c) {
   const LiftDims& d = c.d;
   const dim3 grid(launch_grid(d.N, kBlock, 256L * 8));
-  if (c.gy == nullptr) {
-    hipLaunchKernelGGL((lift_head_fwd_gen_chunk_kernel<double>), grid,
-                       dim3(kBlock), 0, c.stream, c.x.data_ptr<double>(),
-                       c.W1.data_ptr<double>(), c.b1.data_ptr<double>(),
-                       c.W2.data_ptr<double>(), c.b2.data_ptr<double>(),
-                       c.out->data_ptr<double>(), d.C, d.W, d.Ti, d.To, d.S, d.N);
-  } else {
-    hipLaunchKernelGGL((lift_head_bwd_gen_chunk_kernel<double>), grid,
-                       dim3(kBlock), 0, c.stream, c.gy->data_ptr<double>(),
-                       c.x.data_ptr<double>(), c.W1.data_ptr<double>(),
-                       c.b1.data_ptr<double>(), c.W2.data_ptr<double>(),
-                       c.b2.data_ptr<double>(), c.gx->data_ptr<double>(),
-                       c.gW1->data_ptr<double>(), c.gb1->data_ptr<double>(),
-                       c.gW2->data_ptr<double>(), c.gb2->data_ptr<double>(),
-                       d.C, d.W, d.Ti, d.To, d.S, d.N);
-  }
+  select_le<24, 64>(d.W, [&](auto wcap) {
+    constexpr int WCAP = decltype(wcap)::value;
+    if (c.gy == nullptr) {
+      hipLaunchKernelGGL((lift_head_fwd_gen_chunk_kernel<double, WCAP>), grid,
+                         dim3(kBlock), 0, c.stream, c.x.data_ptr<double>(),
+                         c.W1.data_ptr<double>(), c.b1.data_ptr<double>(),
+                         c.W2.data_ptr<double>(), c.b2.data_ptr<double>(),
+                         c.out->data_ptr<double>(), d.C, d.W, d.Ti, d.To, d.S,
+                         d.N);
+    } else {
+      hipLaunchKernelGGL((lift_head_bwd_gen_chunk_kernel<double, WCAP>), grid,
+                         dim3(kBlock), 0, c.stream, c.gy->data_ptr<double>(),
+                         c.x.data_ptr<double>(), c.W1.data_ptr<double>(),
+                         c.b1.data_ptr<double>(), c.W2.data_ptr<double>(),
+                         c.b2.data_ptr<double>(), c.gx->data_ptr<double>(),
+                         c.gW1->data_ptr<double>(), c.gb1->data_ptr<double>(),
+                         c.gW2->data_ptr<double>(), c.gb2->data_ptr<double>(),
+                         d.C, d.W, d.Ti, d.To, d.S, d.N);
+    }
+  });
 }
 
 // kernel family by dtype and entry form

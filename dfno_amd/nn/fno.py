@@ -100,15 +100,20 @@ class DistributedFNONd(nn.Module):
     def _lift(self, x: torch.Tensor) -> torch.Tensor:
         """time lift T_in -> T_out then channel lift C_in -> width, each
         with GELU.  One fused kernel on GPU (ops.lift_head) for T_in <= 16,
-        T_out <= 64, C_in <= 4, width <= 24 in fp32/fp64/bf16; the composed
-        path (recorded as a fallback) otherwise."""
-        from ..ops import lift_head, lift_head_supported
+        T_out <= 64, C_in <= 4: width <= 24 in fp32/fp64/bf16 (the narrow
+        kernel rows), widths 25..64 in fp32/fp64 (the wide rows; bf16 stays
+        composed there by measurement); the composed path (recorded as a
+        fallback, except in bf16) otherwise."""
+        from ..ops import (lift_head, lift_head_supported,
+                           lift_head_wide_range)
         from ..timing import comm_region
         from ..dispatch import note_fallback
 
         l1, l2 = self.linear1, self.linear2
-        if lift_head_supported(x, l1.in_features, l1.out_features,
-                               l2.in_features, l2.out_features):
+        dims = (l1.in_features, l1.out_features, l2.in_features,
+                l2.out_features)
+        if lift_head_supported(x, *dims) or (
+                x.is_cuda and lift_head_wide_range(x.dtype, *dims)):
             with comm_region() as r:
                 W1 = l1.W_bcast(l1.W)
                 b1 = l1.b_bcast(l1.b)

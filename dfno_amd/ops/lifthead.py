@@ -2,7 +2,10 @@
 
 Applies linear1 (time lift T_in -> T_out) + GELU + linear2 (channel lift) +
 GELU in one kernel, for 1 <= T_in <= 16, T_out <= 64, C_in <= 4 and
-width <= 24.  CPU / unsupported shapes use the composed path in the model
+width <= 64: ``lift_head_supported`` is the predicate of the narrow kernel
+rows (width <= 24), ``lift_head_wide_range`` that of the wide ones (width
+25..64; the model routes fp32 and fp64 there, bf16 stays composed by
+measurement).  CPU / unsupported shapes use the composed path in the model
 instead.
 """
 
@@ -12,21 +15,37 @@ import torch
 
 from .. import _ext
 
-__all__ = ["lift_head", "lift_head_supported"]
+__all__ = ["lift_head", "lift_head_supported", "lift_head_wide_range"]
 
 # caps of the kernels (LDS tiles / register arrays are sized by them; the
 # extension re-checks every one before launching)
 MAX_T_IN, MAX_T_OUT, MAX_C_IN, MAX_WIDTH = 16, 64, 4, 24
+# the wide rows of csrc/lift_head.hip (WCAP 64): widths past MAX_WIDTH up to
+WIDE_MAX_WIDTH = 64
 # T_in == 1 with T_out up to this goes in as [B, C, S] (kLaneKMaxTo in
 # csrc/lift_head.hip, which refuses a longer T_out in that form)
 LANE_K_MAX_T_OUT = 32
 
 
 def lift_head_supported(x, t_in, t_out, c_in, width) -> bool:
+    """The narrow kernel rows: a GPU tensor, width <= 24."""
     return (x.is_cuda
             and x.dtype in (torch.float32, torch.float64, torch.bfloat16)
             and 1 <= t_in <= MAX_T_IN and 1 <= t_out <= MAX_T_OUT
             and 1 <= c_in <= MAX_C_IN and 1 <= width <= MAX_WIDTH)
+
+
+def lift_head_wide_range(dtype, t_in, t_out, c_in, width) -> bool:
+    """The wide kernel rows (widths 25..64), as a pure host predicate: the
+    caller checks that the tensor is on the GPU.  bf16 is left out although
+    the kernels take it: at width 64 the fused bf16 forward + backward wins
+    on the flagship lift (2.9 against 11.4 ms) but loses on the Navier-Stokes
+    one (0.81 against 0.65 ms; profiles/optimization_log.md, "Lift head for
+    widths 25-64"), so bf16 models keep the composed lift there."""
+    return (dtype in (torch.float32, torch.float64)
+            and 1 <= t_in <= MAX_T_IN and 1 <= t_out <= MAX_T_OUT
+            and 1 <= c_in <= MAX_C_IN
+            and MAX_WIDTH < width <= WIDE_MAX_WIDTH)
 
 
 class _LiftHeadFn(torch.autograd.Function):
@@ -53,7 +72,9 @@ class _LiftHeadFn(torch.autograd.Function):
 
 
 def lift_head(x, W1, b1, W2, b2):
-    """x: [B, C, *sp, T_in] -> [B, width, *sp, T_out], fully fused."""
+    """x: [B, C, *sp, T_in] -> [B, width, *sp, T_out], fully fused, for
+    every shape either predicate above accepts (the extension raises
+    "unsupported dims" outside them)."""
     B, C = x.shape[0], x.shape[1]
     sp = x.shape[2:-1]
     t_in = x.shape[-1]
