@@ -124,6 +124,28 @@ def main():
     dt = bench(lambda: ext.spectral_corners_bwd_x(ys, ws, xs, starts))
     report("spectral_corners_bwd_x (8 corners)", dt, wbytes + 2 * xbytes)
 
+    # grad-W + Adam of one block's corners: the two-kernel chain (gradient
+    # written, then read back: 7 passes over the weights) against the fused
+    # op (6 passes)
+    gys = torch.randn(1, 20, *F_, device=dev, dtype=torch.complex64)
+    gws = [torch.empty_like(w) for w in ws]
+    ms = [torch.zeros_like(w) for w in ws]
+    vs = [torch.zeros_like(w) for w in ws]
+    flat = lambda ts: [torch.view_as_real(t).view(-1) for t in ts]
+    pf, gf, mf, vf = flat(ws), flat(gws), flat(ms), flat(vs)
+    hyper = (1e-3, 0.9, 0.999, 1e-8, 0.0)
+
+    def chain():
+        ext.spectral_corners_bwd_w(xs, gys, gws, starts)
+        ext.adam_step_batch_(pf, gf, mf, vf, *hyper, [1] * 8)
+
+    dt = bench(chain)
+    report("spectral_corners_bwd_w + adam_step_batch_", dt,
+           7 * wbytes + 2 * xbytes)
+    dt = bench(lambda: ext.spectral_gradw_adam_(xs, gys, ws, ms, vs, starts,
+                                                *hyper, [1] * 8))
+    report("spectral_gradw_adam_ (8 corners)", dt, 6 * wbytes + 2 * xbytes)
+
     # reference: raw copy bandwidth
     src = torch.randn(200_000_000 // 4, device=dev)
     dst = torch.empty_like(src)

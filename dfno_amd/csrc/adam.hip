@@ -12,6 +12,7 @@
 
 #include "kernels.h"
 #include "device_util.h"
+#include "adam_update.h"
 
 // ---------------------------------------------------------------------------
 // fused Adam step (flat real view; complex params are elementwise-identical
@@ -116,10 +117,7 @@ __global__ __launch_bounds__(kBlock) void adam_multi_kernel(
     const float c1 = tab.c1[t], c2 = tab.c2[t];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float gg = gr[k] + wd * pr[k];
-      mr[k] = b1 * mr[k] + (1.f - b1) * gg;
-      vr[k] = b2 * vr[k] + (1.f - b2) * gg * gg;
-      pr[k] -= lr * (mr[k] / c1) / (sqrtf(vr[k] / c2) + eps);
+      adam_update(pr[k], gr[k], mr[k], vr[k], lr, b1, b2, eps, wd, c1, c2);
     }
     *reinterpret_cast<float4*>(tab.p[t] + j) = make_float4(pr[0], pr[1], pr[2], pr[3]);
     *reinterpret_cast<float4*>(tab.m[t] + j) = make_float4(mr[0], mr[1], mr[2], mr[3]);
@@ -161,10 +159,7 @@ __global__ __launch_bounds__(kBlock) void adam_multi_bf16_kernel(
       load8(tab.v[t] + j, vr);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float gg = gr[k] + wd * pr[k];
-        mr[k] = b1 * mr[k] + (1.f - b1) * gg;
-        vr[k] = b2 * vr[k] + (1.f - b2) * gg * gg;
-        pr[k] -= lr * (mr[k] / c1) / (sqrtf(vr[k] / c2) + eps);
+        adam_update(pr[k], gr[k], mr[k], vr[k], lr, b1, b2, eps, wd, c1, c2);
       }
       store8(tab.p[t] + j, pr);
       store8(tab.m[t] + j, mr);
@@ -175,10 +170,7 @@ __global__ __launch_bounds__(kBlock) void adam_multi_bf16_kernel(
         float gv = __uint_as_float(((unsigned int)tab.g[t][e]) << 16);
         float mv = __uint_as_float(((unsigned int)tab.m[t][e]) << 16);
         float vv = __uint_as_float(((unsigned int)tab.v[t][e]) << 16);
-        float gg = gv + wd * pv;
-        mv = b1 * mv + (1.f - b1) * gg;
-        vv = b2 * vv + (1.f - b2) * gg * gg;
-        pv -= lr * (mv / c1) / (sqrtf(vv / c2) + eps);
+        adam_update(pv, gv, mv, vv, lr, b1, b2, eps, wd, c1, c2);
         __hip_bfloat16 hp = __float2bfloat16(pv);
         __hip_bfloat16 hm = __float2bfloat16(mv);
         __hip_bfloat16 hv = __float2bfloat16(vv);
@@ -220,10 +212,7 @@ __global__ __launch_bounds__(kBlock) void adam_multi_uniform_kernel(
     float vr[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float gg = gr[k] + wd * pr[k];
-      mr[k] = b1 * mr[k] + (1.f - b1) * gg;
-      vr[k] = b2 * vr[k] + (1.f - b2) * gg * gg;
-      pr[k] -= lr * (mr[k] / c1) / (sqrtf(vr[k] / c2) + eps);
+      adam_update(pr[k], gr[k], mr[k], vr[k], lr, b1, b2, eps, wd, c1, c2);
     }
     *reinterpret_cast<float4*>(p + j) = make_float4(pr[0], pr[1], pr[2], pr[3]);
     *reinterpret_cast<float4*>(m + j) = make_float4(mr[0], mr[1], mr[2], mr[3]);

@@ -180,6 +180,15 @@ void spectral_corners_bwd_x(const at::Tensor& gy, std::vector<at::Tensor> ws,
 void spectral_corners_bwd_w(const at::Tensor& x, const at::Tensor& gy,
                             std::vector<at::Tensor> gws,
                             std::vector<std::vector<int64_t>> starts);
+// grad-W rebuilt in registers and consumed by the Adam update in one pass
+// (complex64; no gradient tensor is written)
+void spectral_gradw_adam_(const at::Tensor& x, const at::Tensor& gy,
+                          std::vector<at::Tensor> ps,
+                          std::vector<at::Tensor> ms,
+                          std::vector<at::Tensor> vs,
+                          std::vector<std::vector<int64_t>> starts,
+                          double lr, double beta1, double beta2, double eps,
+                          double weight_decay, std::vector<int64_t> steps);
 
 // fp8 (e4m3 packed-pair) spectral-weight variants; device amax per corner
 // (scale = amax/448 computed on device, no host sync)

@@ -23,8 +23,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <cstdlib>
+
 #include "kernels.h"
 #include "device_util.h"
+#include "adam_update.h"
 
 namespace {
 
@@ -267,6 +270,79 @@ __global__ __launch_bounds__(kBlock) void spectral_corners_kernel(
   }
 }
 
+// Element-pair variant (complex64): a thread owns two innermost-consecutive
+// box elements, so the weight stream, x and y all move 16 bytes per lane
+// (a wave touches 1 KB contiguous per access instead of 512 B).  Each
+// element goes through the operations of the kernel above in the same
+// order, so the results are bit-identical.  The host checks what the
+// float4 accesses need (pair_ok) and keeps the kernel above otherwise.
+// mg.cum counts pairs: (nelem / 2) * ntiles per corner.
+template <int OTILE, bool CONJT, int NIN = 0>
+__global__ __launch_bounds__(kBlock) void spectral_corners_pair_kernel(
+    const float* __restrict__ x, MultiGeom<float> mg, float* __restrict__ y,
+    int B, int I, int O, long Ftot) {
+  const int n_out = CONJT ? I : O;
+  const int n_in = NIN > 0 ? NIN : (CONJT ? O : I);
+  const long total = mg.cum[mg.ncorners] * B;
+
+  long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+
+  for (long t = t0; t < total; t += stride) {
+    long work = t % mg.cum[mg.ncorners];
+    int b = (int)(t / mg.cum[mg.ncorners]);
+    int c = 0;
+    while (work >= mg.cum[c + 1]) ++c;
+    work -= mg.cum[c];
+    const BoxGeom& g = mg.g[c];
+    const float* w = mg.w[c];
+    const long npair = g.nelem / 2;
+    const long e = (work % npair) * 2;
+    const int tile = (int)(work / npair);
+
+    const long f = box_to_global(e, g);
+    const int o0 = tile * OTILE;
+    const int olim = min(OTILE, n_out - o0);
+
+    float4 acc[OTILE];   // (re0, im0, re1, im1)
+#pragma unroll
+    for (int k = 0; k < OTILE; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+    const float* xb = x + 2 * (((long)b * n_in) * Ftot + f);
+    auto chan = [&](int i) {
+      const float4 xv = *reinterpret_cast<const float4*>(xb + 2 * (long)i * Ftot);
+#pragma unroll
+      for (int k = 0; k < OTILE; ++k) {
+        if (k < olim) {
+          const long pidx = CONJT
+              ? (((long)(o0 + k)) * O + i) * g.nelem + e
+              : ((long)i * O + o0 + k) * g.nelem + e;
+          const float4 wv = *reinterpret_cast<const float4*>(w + 2 * pidx);
+          if (CONJT) {
+            cmac_conj(acc[k].x, acc[k].y, wv.x, wv.y, xv.x, xv.y);
+            cmac_conj(acc[k].z, acc[k].w, wv.z, wv.w, xv.z, xv.w);
+          } else {
+            cmac(acc[k].x, acc[k].y, xv.x, xv.y, wv.x, wv.y);
+            cmac(acc[k].z, acc[k].w, xv.z, xv.w, wv.z, wv.w);
+          }
+        }
+      }
+    };
+    if constexpr (NIN > 0) {
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) chan(i);
+    } else {
+      for (int i = 0; i < n_in; ++i) chan(i);
+    }
+
+    float* yb = y + 2 * (((long)b * n_out + o0) * Ftot + f);
+#pragma unroll
+    for (int k = 0; k < OTILE; ++k) {
+      if (k < olim) *reinterpret_cast<float4*>(yb + 2 * (long)k * Ftot) = acc[k];
+    }
+  }
+}
+
 // BWD-W: gw[i, o, e] = sum_b gy[b, o, F(e)] * conj(x[b, i, F(e)]) per
 // corner -- at batch ~1 this is a pure per-frequency outer product; fusing
 // the corner gather into the addressing replaces the python-side per-corner
@@ -326,6 +402,116 @@ __global__ __launch_bounds__(kBlock) void spectral_corners_bwd_w_kernel(
   }
 }
 
+// GRAD-W + ADAM: the gradient above is a per-frequency outer product of two
+// small spectra, and Adam is its only reader.  This kernel rebuilds
+// g[i,o,e] in registers (the expressions and b order of the kernel above)
+// and applies adam_update to p/m/v in the same pass, so the gradient tensor
+// never reaches memory: 6 passes over the weight set instead of 7.
+// One thread owns (corner, EPT innermost-consecutive box elements, o) and
+// streams the I input channels.  EPT = 2: every access is 16 bytes per lane
+// (the host checks what that needs); EPT = 1: 8 bytes, any shape.
+// NI > 0 pins I at compile time, as NIN does in spectral_corners_kernel.
+struct GradwAdamTab {
+  BoxGeom g[kMaxCorners];
+  float* p[kMaxCorners];
+  float* m[kMaxCorners];
+  float* v[kMaxCorners];
+  float c1[kMaxCorners], c2[kMaxCorners];   // bias corrections per corner
+  long cum[kMaxCorners + 1];   // cumulative nelem / EPT per corner
+  int ncorners;
+};
+
+template <int EPT>
+__device__ __forceinline__ void ldc(const float* p, float* out) {
+  if constexpr (EPT == 2) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w;
+  } else {
+    const float2 t = *reinterpret_cast<const float2*>(p);
+    out[0] = t.x; out[1] = t.y;
+  }
+}
+
+template <int EPT>
+__device__ __forceinline__ void stc(float* p, const float* v) {
+  if constexpr (EPT == 2) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+  }
+}
+
+template <int NI, int EPT>
+__global__ __launch_bounds__(kBlock) void spectral_gradw_adam_kernel(
+    const float* __restrict__ x, const float* __restrict__ gy,
+    GradwAdamTab tab, int B, int I_, int O, long Ftot, float lr, float b1,
+    float b2, float eps, float wd) {
+  const int I = NI > 0 ? NI : I_;
+  const long total = tab.cum[tab.ncorners] * O;
+  long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+
+  for (long t = t0; t < total; t += stride) {
+    long work = t % tab.cum[tab.ncorners];
+    const int o = (int)(t / tab.cum[tab.ncorners]);
+    int c = 0;
+    while (work >= tab.cum[c + 1]) ++c;
+    const long e = (work - tab.cum[c]) * EPT;
+    const BoxGeom& g = tab.g[c];
+    float* __restrict__ p = tab.p[c];
+    float* __restrict__ m = tab.m[c];
+    float* __restrict__ v = tab.v[c];
+    const float c1 = tab.c1[c], c2 = tab.c2[c];
+
+    const long f = box_to_global(e, g);
+    const float* gy0 = gy + 2 * ((long)o * Ftot + f);
+    const float* x0 = x + 2 * f;
+    float gv0[2 * EPT];
+    ldc<EPT>(gy0, gv0);
+
+    auto chan = [&](int i) {
+      float acc[2 * EPT];
+#pragma unroll
+      for (int k = 0; k < 2 * EPT; ++k) acc[k] = 0.f;
+      for (int b = 0; b < B; ++b) {
+        float gv[2 * EPT], xv[2 * EPT];
+        if (b == 0) {
+#pragma unroll
+          for (int k = 0; k < 2 * EPT; ++k) gv[k] = gv0[k];
+        } else {
+          ldc<EPT>(gy0 + 2 * (long)b * O * Ftot, gv);
+        }
+        ldc<EPT>(x0 + 2 * ((long)b * I + i) * Ftot, xv);
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) {
+          const float xr = xv[2 * k], xi = xv[2 * k + 1];
+          const float gr = gv[2 * k], gi = gv[2 * k + 1];
+          acc[2 * k] += xr * gr + xi * gi;
+          acc[2 * k + 1] += xr * gi - xi * gr;
+        }
+      }
+      const long widx = 2 * (((long)i * O + o) * g.nelem + e);
+      float pr[2 * EPT], mr[2 * EPT], vr[2 * EPT];
+      ldc<EPT>(p + widx, pr);
+      ldc<EPT>(m + widx, mr);
+      ldc<EPT>(v + widx, vr);
+#pragma unroll
+      for (int k = 0; k < 2 * EPT; ++k)
+        adam_update(pr[k], acc[k], mr[k], vr[k], lr, b1, b2, eps, wd, c1, c2);
+      stc<EPT>(p + widx, pr);
+      stc<EPT>(m + widx, mr);
+      stc<EPT>(v + widx, vr);
+    };
+    if constexpr (NI > 0) {
+#pragma unroll
+      for (int i = 0; i < NI; ++i) chan(i);
+    } else {
+#pragma unroll 4
+      for (int i = 0; i < I; ++i) chan(i);
+    }
+  }
+}
+
 
 BoxGeom make_geom(const at::Tensor& x, const at::Tensor& w,
                   const std::vector<int64_t>& starts) {
@@ -351,6 +537,17 @@ BoxGeom make_geom(const at::Tensor& x, const at::Tensor& w,
     g.nelem *= g.box[d];
   }
   return g;
+}
+
+// What the element-pair kernels need of one corner: a 16-byte aligned
+// weight tensor, and pairs that stay inside one innermost row of the box
+// and start on an even element of the spectrum's innermost row.  The
+// spectra themselves must be 16-byte aligned as well (checked by the caller).
+bool pair_ok(const at::Tensor& spec, const at::Tensor& w,
+             const std::vector<int64_t>& starts) {
+  const int64_t last = spec.dim() - 1;
+  return aligned16(w.data_ptr()) && w.size(last) % 2 == 0 &&
+         spec.size(last) % 2 == 0 && starts.back() % 2 == 0;
 }
 
 void check_c(const at::Tensor& t, const char* name) {
@@ -475,8 +672,58 @@ static void launch_corners(const at::Tensor& x,
                            int B, int I, int O, long Ftot,
                            const std::vector<at::Tensor>* amaxes = nullptr) {
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  constexpr int OT = 8;
   const int n_out = CONJT ? I : O;
+  const int n_in = CONJT ? O : I;
+
+  if constexpr (std::is_same<T, float>::value && !FP8) {
+    // element-pair kernel where every corner of the call allows it
+    // (DFNO_SPECTRAL_PAIR=0 keeps the 8-byte kernel, for A/B runs)
+    const char* env = std::getenv("DFNO_SPECTRAL_PAIR");
+    bool pair = !(env && env[0] == '0') && aligned16(x.data_ptr()) &&
+                aligned16(y.data_ptr());
+    for (size_t k = 0; pair && k < ws.size(); ++k)
+      pair = ws[k].dim() == x.dim() &&
+             (int64_t)starts[k].size() == x.dim() - 2 &&
+             (ws[k].numel() == 0 || pair_ok(x, ws[k], starts[k]));
+    // o-tile 4 with half the threads: 4 and 5 measured alike in the step
+    // trace (97 us per call at the flagship), 8 no faster than the 8-byte
+    // kernel (136 us: 88 VGPRs, 5 waves/SIMD)
+    constexpr int ot = 4;
+    if (pair) {
+      size_t idx = 0;
+      while (idx < ws.size()) {
+        MultiGeom<float> mg{};
+        mg.ncorners = 0;
+        mg.cum[0] = 0;
+        const long ntiles = (n_out + ot - 1) / ot;
+        while (idx < ws.size() && mg.ncorners < kMaxCorners) {
+          BoxGeom g = make_geom(x, ws[idx], starts[idx]);
+          if (g.nelem == 0) { ++idx; continue; }
+          int c = mg.ncorners++;
+          mg.g[c] = g;
+          mg.w[c] = reinterpret_cast<const float*>(ws[idx].data_ptr());
+          mg.cum[c + 1] = mg.cum[c] + (g.nelem / 2) * ntiles;
+          ++idx;
+        }
+        if (mg.ncorners == 0) continue;
+        int grid = launch_grid(mg.cum[mg.ncorners] * B, kBlock, 256L * 16);
+#define SPP_LAUNCH(NINV)                                                       \
+        hipLaunchKernelGGL((spectral_corners_pair_kernel<ot, CONJT, NINV>),    \
+                           dim3(grid), dim3(kBlock), 0, stream,                \
+                           reinterpret_cast<const float*>(x.data_ptr()), mg,   \
+                           reinterpret_cast<float*>(y.data_ptr()), B, I, O,    \
+                           Ftot);
+        if (n_in == 20) { SPP_LAUNCH(20) }
+        else if (n_in == 32) { SPP_LAUNCH(32) }
+        else if (n_in == 8) { SPP_LAUNCH(8) }
+        else { SPP_LAUNCH(0) }
+#undef SPP_LAUNCH
+      }
+      return;
+    }
+  }
+
+  constexpr int OT = 8;
   long ntiles = (n_out + OT - 1) / OT;
 
   size_t idx = 0;
@@ -496,7 +743,6 @@ static void launch_corners(const at::Tensor& x,
     }
     if (mg.ncorners == 0) continue;
     int grid = launch_grid(mg.cum[mg.ncorners] * B, kBlock, 256L * 16);
-    const int n_in = CONJT ? O : I;
 #define SPC_LAUNCH(NINV)                                                       \
     hipLaunchKernelGGL((spectral_corners_kernel<T, OT, CONJT, NINV, FP8>),     \
                        dim3(grid), dim3(kBlock), 0, stream,                    \
@@ -695,4 +941,94 @@ void spectral_corners_bwd_x(const at::Tensor& gy, std::vector<at::Tensor> ws,
     launch_corners<double, true>(gy, ws, gx, starts, B, I, O, Ftot);
   }
   DFNO_CHECK_LAUNCH("spectral");
+}
+
+// fused grad-W + Adam over one block's corners (complex64 only): see
+// spectral_gradw_adam_kernel.  ps/ms/vs are the corner weights and their
+// exp_avg / exp_avg_sq, steps the already-incremented step counts.
+void spectral_gradw_adam_(const at::Tensor& x, const at::Tensor& gy,
+                          std::vector<at::Tensor> ps,
+                          std::vector<at::Tensor> ms,
+                          std::vector<at::Tensor> vs,
+                          std::vector<std::vector<int64_t>> starts,
+                          double lr, double beta1, double beta2, double eps,
+                          double weight_decay, std::vector<int64_t> steps) {
+  check_c(x, "x"); check_c(gy, "gy");
+  TORCH_CHECK(x.scalar_type() == at::kComplexFloat &&
+              gy.scalar_type() == at::kComplexFloat,
+              "spectral_gradw_adam_: complex64 only");
+  const size_t n = ps.size();
+  TORCH_CHECK(ms.size() == n && vs.size() == n && starts.size() == n &&
+              steps.size() == n, "spectral_gradw_adam_: list size mismatch");
+  TORCH_CHECK(x.dim() == gy.dim() && x.size(0) == gy.size(0),
+              "spectral_gradw_adam_: x/gy shape mismatch");
+  const int nd = (int)x.dim() - 2;
+  for (int d = 0; d < nd; ++d)
+    TORCH_CHECK(x.size(d + 2) == gy.size(d + 2),
+                "spectral_gradw_adam_: x/gy shape mismatch");
+  int B = (int)x.size(0), I = (int)x.size(1), O = (int)gy.size(1);
+  long Ftot = 1;
+  for (int d = 2; d < x.dim(); ++d) Ftot *= x.size(d);
+  if (B == 0 || n == 0 || I == 0 || O == 0) return;
+
+  // 16-byte accesses: see pair_ok
+  bool vec = aligned16(x.data_ptr()) && aligned16(gy.data_ptr());
+  for (size_t k = 0; k < n; ++k) {
+    const at::Tensor& p = ps[k];
+    check_c(p, "p"); check_c(ms[k], "exp_avg"); check_c(vs[k], "exp_avg_sq");
+    TORCH_CHECK(p.scalar_type() == at::kComplexFloat &&
+                ms[k].scalar_type() == at::kComplexFloat &&
+                vs[k].scalar_type() == at::kComplexFloat,
+                "spectral_gradw_adam_: complex64 only");
+    TORCH_CHECK(p.dim() == x.dim() && (int)p.size(0) == I &&
+                (int)p.size(1) == O, "spectral_gradw_adam_: p shape");
+    TORCH_CHECK(ms[k].sizes() == p.sizes() && vs[k].sizes() == p.sizes(),
+                "spectral_gradw_adam_: state shape");
+    TORCH_CHECK((int)starts[k].size() == nd, "spectral_gradw_adam_: starts");
+    for (int d = 0; d < nd; ++d)
+      TORCH_CHECK(starts[k][d] >= 0 &&
+                  starts[k][d] + p.size(d + 2) <= x.size(d + 2),
+                  "spectral_gradw_adam_: corner box outside the spectrum");
+    vec = vec && pair_ok(x, p, starts[k]) && aligned16(ms[k].data_ptr()) &&
+          aligned16(vs[k].data_ptr());
+  }
+
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int ept = vec ? 2 : 1;
+  size_t idx = 0;
+  while (idx < n) {
+    GradwAdamTab tab{};
+    tab.ncorners = 0;
+    tab.cum[0] = 0;
+    while (idx < n && tab.ncorners < kMaxCorners) {
+      BoxGeom g = make_geom(x, ps[idx], starts[idx]);
+      if (g.nelem == 0) { ++idx; continue; }
+      int c = tab.ncorners++;
+      tab.g[c] = g;
+      tab.p[c] = reinterpret_cast<float*>(ps[idx].data_ptr());
+      tab.m[c] = reinterpret_cast<float*>(ms[idx].data_ptr());
+      tab.v[c] = reinterpret_cast<float*>(vs[idx].data_ptr());
+      tab.c1[c] = (float)(1.0 - std::pow(beta1, (double)steps[idx]));
+      tab.c2[c] = (float)(1.0 - std::pow(beta2, (double)steps[idx]));
+      tab.cum[c + 1] = tab.cum[c] + g.nelem / ept;   // nelem even when ept 2
+      ++idx;
+    }
+    if (tab.ncorners == 0) continue;
+    int grid = launch_grid(tab.cum[tab.ncorners] * O, kBlock, 256L * 32);
+#define SGA_LAUNCH(NI_, EPT_)                                                  \
+    hipLaunchKernelGGL((spectral_gradw_adam_kernel<NI_, EPT_>), dim3(grid),    \
+                       dim3(kBlock), 0, stream,                                \
+                       reinterpret_cast<const float*>(x.data_ptr()),           \
+                       reinterpret_cast<const float*>(gy.data_ptr()), tab, B,  \
+                       I, O, Ftot, (float)lr, (float)beta1, (float)beta2,      \
+                       (float)eps, (float)weight_decay);
+#define SGA_EPT(NI_) if (vec) { SGA_LAUNCH(NI_, 2) } else { SGA_LAUNCH(NI_, 1) }
+    if (I == 20) { SGA_EPT(20) }
+    else if (I == 32) { SGA_EPT(32) }
+    else if (I == 8) { SGA_EPT(8) }
+    else { SGA_EPT(0) }
+#undef SGA_EPT
+#undef SGA_LAUNCH
+  }
+  DFNO_CHECK_LAUNCH("spectral_gradw_adam");
 }

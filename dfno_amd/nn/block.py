@@ -32,6 +32,7 @@ from ..comm import (Repartition, _get_plan, repartition_complete,
                     repartition_issue)
 from ..partition import Partition, compute_distribution_info
 from ..ops import spectral_conv, linear_res_gelu, rfft_trunc, fft_trunc, pad_ifft, pad_irfft
+from ..ops.spectral import CORNER_TAG
 from ..ops import block_epilogue, fused_epilogue_enabled, fused_epilogue_ok
 from ..ops.fft import (new_stash_key, rfft_bf16_native_ok, rfft_trunc_stash,
                        stash_fusable, zt_caps_ok, zt_enabled, zt_fwd, zt_inv,
@@ -146,6 +147,9 @@ class DistributedFNOBlock(nn.Module):
                 self.scale * torch.rand(self.width, self.width,
                                         *[b - a for a, b in bounds],
                                         device=device, dtype=self.dtype_complex))
+            # lets dfno_amd.optim.Adam take grad-W of these inside its update
+            # (ops/spectral.py, "Deferred grad-W")
+            setattr(w, CORNER_TAG, True)
             self.weights.append(w)
             self.corner_bounds.append(bounds)
             self.slices.append([slice(None), slice(None)] + [slice(a, b) for a, b in bounds])

@@ -9,19 +9,35 @@ The contraction is, per kept frequency point f:
     y[b, o, f] = sum_i x[b, i, f] * w[i, o, f]
 i.e. a width x width complex matvec batched over frequencies.  At batch 1 and
 width ~20 this is HBM-bandwidth-bound on the *weight* stream (intensity
-~1 flop/byte), so the native kernel is a vectorized streaming VALU kernel
-(float4 = 2 complex per load) with the corner-box gather/scatter fused into
-its addressing — the truncated spectrum is touched exactly once and no
+~1 flop/byte), so the native kernel is a streaming VALU kernel (complex64
+with even innermost extents: two complex weights, 16 bytes, per lane and
+load; one otherwise) with the corner-box gather/scatter fused into its
+addressing — the truncated spectrum is touched exactly once and no
 per-corner slices are materialized.  (An MFMA formulation does not pay here:
 each weight element is used `batch` times only, far below the fp32 ridge.)
 
 Autograd: grad_x[b,i,f] = sum_o conj(w[i,o,f]) gy[b,o,f] (same kernel,
 conjugate-transposed weight); grad_w[i,o,f] = sum_b conj(x[b,i,f]) gy[b,o,f]
-(library einsum over the corner views).
+(``spectral_corners_bwd_w``: one thread per (corner, frequency, o), with the
+corner gather fused into the addressing).
+
+Deferred grad-W.  grad_w is a per-frequency outer product of two small
+spectra, and at batch 1 the optimizer is its only reader.  When every corner
+weight of a call belongs to one ``dfno_amd.optim.Adam`` (``register_corners``)
+the backward does not build it: it hands ``(x, gy, starts, weights)`` to that
+optimizer as a pending entry and returns ``None`` for the weights, and
+``Adam.step()`` rebuilds the gradient in registers inside the update kernel
+(``spectral_gradw_adam_``).  With such an optimizer ``.grad`` of the corner
+weights is therefore ``None`` after ``backward()`` and post-accumulate hooks
+on them do not fire; ``Adam.materialize_grads()`` writes the gradients out
+for callers who inspect or clip them.  ``DFNO_FUSED_SPECTRAL_ADAM=0``
+restores the eager gradient.
 """
 
 from __future__ import annotations
 
+import os
+import weakref
 from typing import List, Sequence, Tuple
 
 import torch
@@ -104,6 +120,63 @@ def dequantize_fp8(w16: torch.Tensor, amax) -> torch.Tensor:
     return torch.view_as_complex(w8.to(torch.float32) * scale)
 
 
+# ---------------------------------------------------------------------------
+# deferred grad-W: which optimizer owns which corner weight
+# ---------------------------------------------------------------------------
+
+CORNER_TAG = "_dfno_spectral_corner"   # set by DistributedFNOBlock
+_CORNER_OWNER = {}   # id(w) -> (weakref(w), weakref(optimizer))
+
+
+def fused_spectral_adam_enabled() -> bool:
+    return os.environ.get("DFNO_FUSED_SPECTRAL_ADAM", "1") != "0"
+
+
+def register_corners(optimizer, params) -> None:
+    """Record ``optimizer`` as the owner of the tagged complex64 corner
+    weights among ``params`` (weakly: neither side is kept alive)."""
+    dead = [k for k, (wr, orf) in _CORNER_OWNER.items()
+            if wr() is None or orf() is None]
+    for k in dead:
+        del _CORNER_OWNER[k]
+    for p in params:
+        if getattr(p, CORNER_TAG, False) and p.dtype == torch.complex64:
+            _CORNER_OWNER[id(p)] = (weakref.ref(p), weakref.ref(optimizer))
+
+
+def _corner_owner(weights):
+    """The live optimizer every one of ``weights`` is registered with, or
+    None."""
+    owner = None
+    for w in weights:
+        ent = _CORNER_OWNER.get(id(w))
+        if ent is None or ent[0]() is not w:
+            return None
+        opt = ent[1]()
+        if opt is None or (owner is not None and opt is not owner):
+            return None
+        owner = opt
+    return owner
+
+
+def corner_grads(x, gy, bounds_list, weights):
+    """grad-W of every corner: the native kernel on GPU (in_channels <= 64),
+    the einsum otherwise."""
+    if (gy.is_cuda and gy.numel() > 0 and x.shape[1] <= 64
+            and gy.dtype in (torch.complex64, torch.complex128)):
+        ext = _ext.get(required=True)
+        gws = [torch.empty_like(w) for w in weights]
+        ext.spectral_corners_bwd_w(
+            x.contiguous(), gy, gws,
+            [[a for a, _ in bounds] for bounds in bounds_list])
+        return gws
+    gws = []
+    for w, bounds in zip(weights, bounds_list):
+        sl = _corner_slices(bounds)
+        gws.append(torch.einsum("bo...,bi...->io...", gy[sl], x[sl].conj()))
+    return gws
+
+
 class _SpectralConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, bounds_list, out_channels: int,
@@ -138,7 +211,39 @@ class _SpectralConvFn(torch.autograd.Function):
                 y[sl] = torch.einsum("bi...,io...->bo...", x[sl], w)
         ctx.save_for_backward(x_saved, *weights)
         ctx.bounds_list = bounds_list
+        # the Parameter objects themselves (saved tensors may be unpacked
+        # into new objects), kept only where a deferral is possible at all
+        ctx.corner_params = (
+            weights if weights and not fp8 and x.dtype == torch.complex64
+            and _corner_owner(weights) is not None else None)
         return y
+
+    @staticmethod
+    def _deferral_owner(ctx, x):
+        """The optimizer that takes this call's grad-W as a pending entry, or
+        None when the gradient has to be built now."""
+        params = ctx.corner_params
+        if params is None or not fused_spectral_adam_enabled():
+            return None
+        if torch.is_grad_enabled() or x.shape[1] > 64:   # create_graph
+            return None
+        if not all(ctx.needs_input_grad[4:]):
+            return None
+        opt = _corner_owner(params)
+        if opt is None:
+            return None
+        if opt.has_pending(params):
+            # a second backward before step(): autograd has to accumulate,
+            # so the first gradient is written out and this one follows it
+            opt.materialize_grads()
+            return None
+        for w in params:
+            ent = _FP8_CACHE.get(id(w))
+            if w.grad is not None or (ent is not None
+                                      and ent[1].shape == w.shape
+                                      and ent[1].device == w.device):
+                return None   # accumulate / keep the e4m3 side table path
+        return opt if opt.accepts_deferred(params) else None
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
@@ -148,6 +253,9 @@ class _SpectralConvFn(torch.autograd.Function):
         gy = gy.contiguous()
         gx = torch.zeros_like(x)
         gws = []
+        owner = _SpectralConvFn._deferral_owner(ctx, x)
+        if owner is not None:
+            gws = [None] * len(weights)
         if gy.is_cuda and gy.numel() > 0 and gy.dtype in (torch.complex64, torch.complex128):
             ext = _ext.get(required=True)
             starts = [[a for a, _ in bounds] for bounds in bounds_list]
@@ -157,22 +265,20 @@ class _SpectralConvFn(torch.autograd.Function):
             else:
                 ext.spectral_corners_bwd_x(
                     gy, [w.contiguous() for w in weights], gx, starts)
-            if x.shape[1] <= 64:
-                gws = [torch.empty_like(w) for w in weights]
-                ext.spectral_corners_bwd_w(x.contiguous(), gy, gws, starts)
-            else:
-                from ..dispatch import note_fallback
-                note_fallback("spectral_corners_bwd_w",
-                              f"in_channels {x.shape[1]} > 64 (einsum grad-W)")
-                for w, bounds in zip(weights, bounds_list):
-                    sl = _corner_slices(bounds)
-                    gws.append(torch.einsum("bo...,bi...->io...",
-                                            gy[sl], x[sl].conj()))
+            if owner is None:
+                if x.shape[1] > 64:
+                    from ..dispatch import note_fallback
+                    note_fallback("spectral_corners_bwd_w",
+                                  f"in_channels {x.shape[1]} > 64 (einsum grad-W)")
+                gws = corner_grads(x, gy, bounds_list, weights)
         else:
             for w, bounds in zip(weights, bounds_list):
                 sl = _corner_slices(bounds)
                 gx[sl] = torch.einsum("bo...,io...->bi...", gy[sl], w.conj())
-                gws.append(torch.einsum("bo...,bi...->io...", gy[sl], x[sl].conj()))
+            if owner is None:
+                gws = corner_grads(x, gy, bounds_list, weights)
+        if owner is not None:
+            owner.add_pending(x, gy, bounds_list, ctx.corner_params)
         return (gx, None, None, None, *gws)
 
 

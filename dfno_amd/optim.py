@@ -6,6 +6,15 @@ fp32/complex64 parameters the update runs as one fused HIP kernel per
 parameter over flat real views (complex Adam is elementwise-identical on
 the real view), ~3x less optimizer overhead than the foreach path at the
 flagship config.  Any other parameter falls back to the stock step.
+
+Spectral corner weights (tagged by ``DistributedFNOBlock``, complex64) are
+registered with the optimizer that owns them.  Their backward then leaves a
+pending ``(x, gy)`` entry here instead of a gradient tensor, and ``step()``
+runs one kernel per entry that rebuilds the gradient in registers and applies
+the update (ops/spectral.py, "Deferred grad-W").  ``.grad`` of those weights
+stays ``None``; ``materialize_grads()`` writes the gradients out on request,
+``zero_grad()`` drops the pending entries, and ``DFNO_FUSED_SPECTRAL_ADAM=0``
+turns the deferral off.
 """
 
 from __future__ import annotations
@@ -13,6 +22,7 @@ from __future__ import annotations
 import torch
 
 from . import _ext
+from .ops import spectral as _spectral
 
 __all__ = ["Adam"]
 
@@ -26,6 +36,87 @@ class Adam(torch.optim.Adam):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._flat_cache = {}  # id(p) -> (ptrs, (pv, mv, vv))
+        # deferred spectral grad-W: (x, gy, bounds_list, weights) per call
+        self._pending = []
+        for group in self.param_groups:
+            _spectral.register_corners(self, group["params"])
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if hasattr(self, "_pending"):   # not during __init__
+            _spectral.register_corners(self, self.param_groups[-1]["params"])
+
+    # ---- deferred spectral grad-W ----------------------------------------
+    def _group_of(self, p):
+        for group in self.param_groups:
+            if any(q is p for q in group["params"]):
+                return group
+        return None
+
+    def accepts_deferred(self, weights) -> bool:
+        """Whether ``step()`` can take these corner weights without a
+        gradient tensor: one plain (not amsgrad, not maximize) group."""
+        group = self._group_of(weights[0])
+        return (group is not None
+                and not group.get("amsgrad", False)
+                and not group.get("maximize", False)
+                and all(any(q is w for q in group["params"]) for w in weights))
+
+    def has_pending(self, weights) -> bool:
+        ids = {id(w) for w in weights}
+        return any(id(w) in ids for ent in self._pending for w in ent[3])
+
+    def add_pending(self, x, gy, bounds_list, weights) -> None:
+        self._pending.append((x, gy, bounds_list, tuple(weights)))
+
+    @torch.no_grad()
+    def materialize_grads(self) -> None:
+        """Write every pending corner gradient into ``.grad`` (accumulating
+        onto an existing one) and clear the pending entries."""
+        pending, self._pending = self._pending, []
+        for x, gy, bounds_list, weights in pending:
+            for w, gw in zip(weights, _spectral.corner_grads(
+                    x, gy, bounds_list, weights)):
+                if w.grad is None:
+                    w.grad = gw
+                else:
+                    w.grad += gw
+
+    def zero_grad(self, set_to_none: bool = True):
+        self._pending = []
+        return super().zero_grad(set_to_none=set_to_none)
+
+    def _step_pending(self, ext) -> None:
+        """One fused grad-W + Adam launch per pending entry."""
+        pending, self._pending = self._pending, []
+        for ent in pending:
+            x, gy, bounds_list, weights = ent
+            group = self._group_of(weights[0])
+            if (not x.is_cuda or x.numel() == 0
+                    or any(w.grad is not None or not w.is_contiguous()
+                           for w in weights)):
+                self._pending = [ent]
+                self.materialize_grads()
+                continue
+            ms, vs, steps = [], [], []
+            for w in weights:
+                state = self.state[w]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0)
+                    state["exp_avg"] = torch.zeros_like(w)
+                    state["exp_avg_sq"] = torch.zeros_like(w)
+                state["step"] += 1
+                ms.append(state["exp_avg"])
+                vs.append(state["exp_avg_sq"])
+                steps.append(int(state["step"].item()))
+            beta1, beta2 = group["betas"]
+            for i in range(0, len(weights), 8):
+                ext.spectral_gradw_adam_(
+                    x, gy, [w.detach() for w in weights[i:i + 8]],
+                    ms[i:i + 8], vs[i:i + 8],
+                    [[a for a, _ in b] for b in bounds_list[i:i + 8]],
+                    group["lr"], beta1, beta2, group["eps"],
+                    group["weight_decay"], steps[i:i + 8])
 
     def _flat_views(self, p, state):
         def flat(t):
@@ -49,6 +140,11 @@ class Adam(torch.optim.Adam):
                 loss = closure()
 
         ext = _ext.get(required=False) if torch.cuda.is_available() else None
+        if self._pending:
+            if ext is None:
+                self.materialize_grads()   # CPU: the stock path below
+            else:
+                self._step_pending(ext)
         fallback_groups = []
         for group in self.param_groups:
             lr = group["lr"]

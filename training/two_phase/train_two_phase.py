@@ -106,7 +106,10 @@ def main():
         P_x, [nb, channel_in, *shape[:-1], 1], shape[-1], args.width,
         tuple(args.modes), device=device, dtype=dtype)
     criterion = dfno.DistributedRelativeLpLoss(P_x)
-    optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
+    # same state layout as torch.optim.Adam (old checkpoints load); fused
+    # updates, and grad-W of the spectral weights folded into them
+    from dfno_amd.optim import Adam
+    optimizer = Adam(model.parameters(), lr=args.lr)
 
     out_dir = Path(args.out_dir)
     if P_root.active:
