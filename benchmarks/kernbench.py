@@ -79,6 +79,12 @@ def main():
     # fully-fused head backward (no gz3 in HBM; reads x+gy, writes gx)
     dt = bench(lambda: ext.proj_head_bwd_fused(gy, x, W3, b3, W4))
     report("proj_head_bwd_fused", dt, (20 + 1 + 20) * S * 4)
+    # the two-output instantiation (O2T = 2)
+    W42 = torch.randn(2, 128, device=dev) / 128
+    gy2 = torch.randn(1, 2, S, device=dev)
+    dt = bench(lambda: ext.proj_head_bwd_fused(gy2, x, W3, b3, W42))
+    report("proj_head_bwd_fused, 2 outputs", dt, (20 + 2 + 20) * S * 4)
+    del gy2
 
     # fused trunk mix backward (gz as an LDS tile; gz streamed = res grad)
     zmix = torch.randn(1, 20, S, device=dev)

@@ -49,12 +49,27 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
   constexpr int LD = TS + 4;
   extern __shared__ __align__(16) char smem_raw[];
   float* gzt = reinterpret_cast<float*>(smem_raw);   // [C][LD]
-  float* xt = gzt + (size_t)C * LD;                  // [C][LD]
+  float* xt = gzt + (size_t)C * LD;                  // [C + 1][LD]
+  // row C of xt is all ones (phase B's gb column); staging never writes it
+  if (threadIdx.x < TS) xt[C * LD + threadIdx.x] = 1.f;
 
   const int lane = (int)(threadIdx.x & 63);
   const int wave = (int)(threadIdx.x >> 6);
   const int l16 = lane & 15;
   const int kg = lane >> 4;
+
+  // MFMA operands are loaded unconditionally.  Output row m of an MFMA
+  // depends only on A row m and output column n only on B column n, and
+  // the padded rows and columns (>= C, or > C with the ones row) are
+  // dropped at the gx store and at the flush: their lanes read a clamped,
+  // in-bounds row instead of a masked zero.
+  // phase A's A fragments, W^T for the wave's two m-tiles: tile-invariant
+  float wa[2][C / 4];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int ks = 0; ks < C / 4; ++ks)
+      wa[mt][ks] = WX ? W[(4 * ks + kg) * C + min(mt * 16 + l16, C - 1)] : 0.f;
 
   // gW/gb fragments: M = 2 o-tiles, N = 2 tiles (i channels + ones col)
   f32x4 wacc;
@@ -113,48 +128,45 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
     }
     prefetch(t + gridDim.x);
     __syncthreads();
-    // phase A: gx = W^T @ gz.  A[m=i][k=o] = W[o*C+i] (per-lane global,
-    // L1-resident), B[n=c][k=o] = gzt[o][c]; K = C padded to 24.
+    // phase A: gx = W^T @ gz.  A[m=i][k=o] = W[o*C+i] (wa, registers),
+    // B[n=c][k=o] = gzt[o][c]; K = C (4-aligned).  The wave's two pairs
+    // (m-tiles 0 and 1) share n-tile `wave`: one gz fragment per k-step.
+    if constexpr (WX) {
+      const int n = wave * 16 + l16;
+      f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int pp = 0; pp < (WX ? (2 * (TS / 16)) / 4 : 0); ++pp) {
-      const int p = wave + 4 * pp;
-      const int mt = p / (TS / 16), nt = p % (TS / 16);
-      const int m = mt * 16 + l16;
-      const int n = nt * 16 + l16;
-      const bool av = m < C;
-      f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < C; k += 4) {       // C = 20: K is 4-aligned
-        const int ko = k + kg;
-        const float a = av ? W[ko * C + m] : 0.f;
-        const float bb = gzt[ko * LD + n];
-        c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, c4, 0, 0, 0);
+      for (int ks = 0; ks < C / 4; ++ks) {
+        const float bb = gzt[(4 * ks + kg) * LD + n];
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[0][ks], bb, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][ks], bb, c1, 0, 0, 0);
       }
-      const long sc = s0 + nt * 16 + l16;
+      const long sc = s0 + n;
       if (sc < S) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int i = mt * 16 + kg * 4 + r;
-          if (i < C) st(gx + ((long)b * C + i) * S + sc, c4[r]);
+          st(gx + ((long)b * C + kg * 4 + r) * S + sc, c0[r]);
+          if (16 + kg * 4 + r < C)
+            st(gx + ((long)b * C + 16 + kg * 4 + r) * S + sc, c1[r]);
         }
       }
     }
     // phase B: gW fragments += gz @ [x; ones]^T.  One (mt, nt) pair per
-    // wave: mt = wave>>1 (o-tiles), nt = wave&1 (i-tiles; col C = ones
-    // for gb).
+    // wave: mt = wave>>1 (o-tiles), nt = wave&1 (i-tiles; col C = the ones
+    // row, for gb).  Both operands run along the tile row: lane group kg
+    // takes columns 16*g + 4*kg .. +3 in four successive MFMAs, the same k
+    // order for A and B, so one ds_read_b128 each serves four k-steps.
     {
       const int mt = wave >> 1, nt = wave & 1;
-      const float* gr = gzt + (mt * 16 + l16) * LD;
-      const int ncol = nt * 16 + l16;
-      const float* xr = xt + ncol * LD;
-      const bool av = (mt * 16 + l16) < C;
-      const bool bx = ncol < C;
-      const bool bones = ncol == C;
-#pragma unroll 8
-      for (int k = 0; k < TS; k += 4) {
-        const float a = av ? gr[k + kg] : 0.f;
-        const float bb = bx ? xr[k + kg] : (bones ? 1.f : 0.f);
-        wacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, wacc, 0, 0, 0);
+      const float* gr = gzt + min(mt * 16 + l16, C - 1) * LD + 4 * kg;
+      const float* xr = xt + min(nt * 16 + l16, C) * LD + 4 * kg;
+#pragma unroll
+      for (int g = 0; g < TS / 16; ++g) {
+        const float4 a = *reinterpret_cast<const float4*>(gr + 16 * g);
+        const float4 bb = *reinterpret_cast<const float4*>(xr + 16 * g);
+        wacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bb.x, wacc, 0, 0, 0);
+        wacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bb.y, wacc, 0, 0, 0);
+        wacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bb.z, wacc, 0, 0, 0);
+        wacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bb.w, wacc, 0, 0, 0);
       }
     }
   }
@@ -176,8 +188,8 @@ __global__ __launch_bounds__(kBlock, 4) void mix_bwd_fused_kernel(
 }
 
 // One launch of mix_bwd_fused_kernel<TIO, WG, WX>: grid-stride over the
-// B * ceil(S / 64) tiles with at most 1024 blocks (4 per CU), the gz and x
-// tiles [20][68] fp32 in dynamic LDS.  An output the instantiation never
+// B * ceil(S / 64) tiles with at most 1024 blocks (4 per CU), the gz tile
+// [20][68] and the x tile plus its ones row [21][68] fp32 in dynamic LDS.  An output the instantiation never
 // stores (gz without WG, gx without WX) goes in as null.
 template <typename TIO, bool WG, bool WX>
 void launch_mix_bwd(const at::Tensor& gy, const at::Tensor& z,
@@ -185,7 +197,7 @@ void launch_mix_bwd(const at::Tensor& gy, const at::Tensor& z,
                     at::Tensor& gW, float* gb, at::Tensor& gz, int B, long S) {
   const long stiles = (S + kTile - 1) / kTile;
   const int grid = (int)std::min((long)B * stiles, 1024L);
-  const size_t smem = sizeof(float) * 2 * 20 * (kTile + 4);
+  const size_t smem = sizeof(float) * (2 * 20 + 1) * (kTile + 4);
   hipLaunchKernelGGL((mix_bwd_fused_kernel<TIO, WG, WX>), dim3(grid),
                      dim3(kBlock), smem,
                      at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(),

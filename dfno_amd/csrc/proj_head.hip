@@ -329,6 +329,37 @@ __global__ __launch_bounds__(kBlock) void proj_head_bwd_kernel(
 // v_mfma_f32_16x16x4 on the LDS tile with per-wave fragment accumulators
 // carried across tiles (identical numerics to the library chain up to
 // fp32 atomic reduction order, like every gw kernel here).
+//
+// Per 64-column tile, 4 waves (lane = kg*16 + l16), block barriers between
+// the phases:
+//   stage  x / gy columns, prefetched into registers during the previous
+//          tile, go to LDS (xt, gyt); gb4 partials accumulate on the way.
+//   1a     z3 = W3 @ x.  Wave w owns m-tiles 2w and 2w+1 for all four
+//          n-tiles: its ten W3 fragments sit in registers for the whole
+//          kernel, each x fragment is read once per (n-tile, k-step) and
+//          feeds both m-tiles, and the eight chains run independently.
+//   1b     gz = (W4^T gy) * gelu'(z3 + b3) in place (VALU); gb3 / gW4
+//          partials per thread pair.
+//   2a     gx = W3^T @ gz, K = 128.  Wave w owns n-tile w for both m-tiles
+//          (channels 0..15 and 16..19): one gz fragment per k-step feeds two
+//          chains; the W3 fragments come as one ds_read_b128 per four
+//          k-steps from an LDS image in fragment order (W3f, W3g).
+//   2b     gW3 += gz @ x^T, K = 64 columns.  Wave w owns x n-tile w&1 and
+//          gz m-tiles (w>>1) + 2p: one x fragment feeds four chains.  Both
+//          operands run along the tile row, so lane group kg takes columns
+//          16g + 4kg .. +3 in four successive MFMAs (the same k order for A
+//          and B) and one ds_read_b128 each serves four k-steps.
+// The order in which any gx element is summed (k ascending, one chain from
+// zero) is the plain one; only the gW3 column order inside a tile is
+// permuted, and gW3 is summed over tiles and blocks in atomic order anyway.
+//
+// MFMA operands are loaded unconditionally.  Output row m of an MFMA
+// depends only on A row m, output column n only on B column n, and the
+// padded rows and columns (channel i >= 20) are dropped at the gx store and
+// at the gW3 flush.  So the padded lanes read some in-bounds LDS word (a
+// clamped row, or a repeat of rows 16..19 in W3g) with no exec mask and no
+// zero: a masked operand read puts every MFMA in a basic block of its own
+// with a full lgkmcnt(0) wait in front of it.
 // ---------------------------------------------------------------------------
 
 template <int IT, int MT, int O2T, typename TIO = float>
@@ -339,6 +370,8 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
     TIO* __restrict__ gx, float* __restrict__ gW3,
     float* __restrict__ gb3, float* __restrict__ gW4,
     float* __restrict__ gb4, int B, int O2, long S) {
+  static_assert(IT == 20 && MT == 128,
+                "fragment maps: 4 waves x 2 m-tiles, channels 16..19 padded");
   constexpr int TS = 64;           // s-columns per tile (16 MFMA K-steps)
   constexpr int LD = TS + 4;       // row pad (float4-aligned, 4-bank skew)
   // gz tile + staged x tile + weights in LDS (52 KB -> 3 blocks/CU; an
@@ -348,13 +381,25 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
   float* gzt = reinterpret_cast<float*>(smem_raw);   // [MT][LD]
   float* xt = gzt + (size_t)MT * LD;                 // [IT][LD]
   float* gyt = xt + (size_t)IT * LD;                 // [O2T][TS]
-  float* W3l = gyt + O2T * TS;                       // [MT*IT]
-  float* b3l = W3l + (size_t)MT * IT;                // [MT]
+  float* W3f = gyt + O2T * TS;                       // [MT/16][64][4]
+  float* W3g = W3f + (size_t)MT * 16;                // [MT/16][4][IT-16][4]
+  float* b3l = W3g + (size_t)MT * (IT - 16);         // [MT]
   float* W4l = b3l + MT;                             // [O2T*MT]
   float* gb3s = W4l + O2T * MT;                      // [MT]
   float* gW4s = gb3s + MT;                           // [O2T*MT]
+  // W3 in phase 2a's A-fragment order, k = j = 16*g + 4*e + kg: W3f holds
+  // rows i < 16 as [g][lane = kg*16 + i][e], W3g rows 16..IT-1 as
+  // [g][kg][i - 16][e]; one ds_read_b128 each serves four k-steps
 #pragma clang loop unroll(disable)
-  for (int k = threadIdx.x; k < MT * IT; k += kBlock) W3l[k] = W3[k];
+  for (int k = threadIdx.x; k < MT * 16; k += kBlock) {
+    const int e = k & 3, ln = (k >> 2) & 63, g = k >> 8;
+    W3f[k] = W3[(16 * g + 4 * e + (ln >> 4)) * IT + (ln & 15)];
+  }
+#pragma clang loop unroll(disable)
+  for (int k = threadIdx.x; k < MT * (IT - 16); k += kBlock) {
+    const int e = k & 3, r = (k >> 2) & 3, q = (k >> 4) & 3, g = k >> 6;
+    W3g[k] = W3[(16 * g + 4 * e + q) * IT + 16 + r];
+  }
   for (int k = threadIdx.x; k < MT; k += kBlock) {
     b3l[k] = b3[k];
     gb3s[k] = 0.f;
@@ -373,6 +418,14 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
 #pragma unroll
   for (int p = 0; p < 4; ++p) wacc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
   float gb4a0 = 0.f, gb4a1 = 0.f;
+  // phase 1a A fragments: the wave's m-tiles 2*wave and 2*wave+1 of W3,
+  // the same for every tile
+  float w3a[2][IT / 4];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ks = 0; ks < IT / 4; ++ks)
+      w3a[mi][ks] = W3[((2 * wave + mi) * 16 + l16) * IT + 4 * ks + kg];
 
   const long stiles = (S + TS - 1) / TS;
   const long tend = (long)B * stiles;
@@ -422,23 +475,31 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
     prefetch(t + gridDim.x);
     __syncthreads();               // xt/gyt staged
     // phase 1a: z3 tile = W3 @ x via MFMA (bias-free, into gzt).
-    // 8 m-tiles x 4 n-tiles over K = IT = 20; 8 pairs per wave.
+    // 8 m-tiles x 4 n-tiles over K = IT = 20; the wave's two m-tiles x all
+    // four n-tiles as eight independent chains, x fragments shared.
+    {
+      f32x4 z4[2][4];
 #pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-      const int p = wave + 4 * pp;
-      const int mt = p >> 2, nt = p & 3;
-      const int m = mt * 16 + l16;
-      const int n = nt * 16 + l16;
-      f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+      for (int q = 0; q < 8; ++q) z4[q >> 2][q & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int k = 0; k < IT; k += 4) {
-        const float a = W3l[m * IT + k + kg];
-        const float bb = xt[(k + kg) * LD + n];
-        z4 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, z4, 0, 0, 0);
+      for (int ks = 0; ks < IT / 4; ++ks) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const float bb = xt[(4 * ks + kg) * LD + nt * 16 + l16];
+#pragma unroll
+          for (int mi = 0; mi < 2; ++mi)
+            z4[mi][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                w3a[mi][ks], bb, z4[mi][nt], 0, 0, 0);
+        }
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        gzt[(mt * 16 + kg * 4 + r) * LD + nt * 16 + l16] = z4[r];
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            gzt[((2 * wave + mi) * 16 + kg * 4 + r) * LD + nt * 16 + l16] =
+                z4[mi][nt][r];
     }
     __syncthreads();
     // phase 1b: gz = (W4^T gy) * gelu'(z3 + b3) in place over the tile.
@@ -487,46 +548,61 @@ __global__ __launch_bounds__(kBlock, 3) void proj_head_bwd_fused_kernel(
       }
     }
     __syncthreads();
-    // phase 2a: gx tile = W3^T @ gz via MFMA.  A[m=i][k=j] = W3[k*IT+m]
-    // (per-lane global), B[n=c][k=j] = gzt[k*LD+n]; K = MT.
+    // phase 2a: gx tile = W3^T @ gz via MFMA.  A[m=i][k=j] = W3[k*IT+m],
+    // B[n=c][k=j] = gzt[k*LD+n]; K = MT.  A wave's two pairs (m-tiles 0
+    // and 1) share the n-tile: one gz fragment per k-step, two chains.
+    {
+      const int n = wave * 16 + l16;
+      const float* a0p = W3f + lane * 4;
+      const float* a1p = W3g + (kg * 4 + (l16 & 3)) * 4;
+      f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+      for (int g = 0; g < MT / 16; ++g) {
+        const float4 a0 = *reinterpret_cast<const float4*>(a0p + g * 256);
+        const float4 a1 = *reinterpret_cast<const float4*>(a1p + g * 64);
+        const float a0e[4] = {a0.x, a0.y, a0.z, a0.w};
+        const float a1e[4] = {a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-      const int p = wave + 4 * pp;
-      const int mt = p >> 2, nt = p & 3;
-      const int m = mt * 16 + l16;
-      const int n = nt * 16 + l16;
-      const bool av = m < IT;
-      f32x4 c4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-      for (int k = 0; k < MT; k += 4) {
-        const float a = av ? W3l[(k + kg) * IT + m] : 0.f;
-        const float bb = gzt[(k + kg) * LD + n];
-        c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, c4, 0, 0, 0);
+        for (int e = 0; e < 4; ++e) {
+          const float bb = gzt[(16 * g + 4 * e + kg) * LD + n];
+          c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0e[e], bb, c0, 0, 0, 0);
+          c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1e[e], bb, c1, 0, 0, 0);
+        }
       }
-      const long sc = s0 + nt * 16 + l16;
+      const long sc = s0 + n;
       if (sc < S) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int i = mt * 16 + kg * 4 + r;
-          if (i < IT) st(gx + ((long)b * IT + i) * S + sc, c4[r]);
+          st(gx + ((long)b * IT + kg * 4 + r) * S + sc, c0[r]);
+          if (16 + kg * 4 + r < IT)
+            st(gx + ((long)b * IT + 16 + kg * 4 + r) * S + sc, c1[r]);
         }
       }
     }
     // phase 2b: gW3 fragments += gz_tile @ x_tile^T (reads only; the
-    // tile loop's top sync fences the next staging pass)
+    // tile loop's top sync fences the next staging pass).  A wave's four
+    // pairs share the x n-tile: one x fragment per k-step, four chains.
+    {
+      const float* gr = gzt + ((wave >> 1) * 16 + l16) * LD + 4 * kg;
+      const float* xr =
+          xt + min((wave & 1) * 16 + l16, IT - 1) * LD + 4 * kg;
+#pragma unroll 2
+      for (int g = 0; g < TS / 16; ++g) {
+        const float4 xb = *reinterpret_cast<const float4*>(xr + 16 * g);
+        const float xe[4] = {xb.x, xb.y, xb.z, xb.w};
+        float4 ga[4];
 #pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-      const int p = wave + 4 * pp;
-      const int mt = p >> 1, nt = p & 1;
-      const float* gr = gzt + (mt * 16 + l16) * LD;
-      const float* xr = xt + (nt * 16 + l16) * LD;
-      const bool bv = (nt * 16 + l16) < IT;
-#pragma unroll 8
-      for (int k = 0; k < TS; k += 4) {
-        const float a = gr[k + kg];
-        const float bb = bv ? xr[k + kg] : 0.f;
-        wacc[pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb, wacc[pp],
-                                                        0, 0, 0);
+        for (int pp = 0; pp < 4; ++pp)
+          ga[pp] = *reinterpret_cast<const float4*>(gr + pp * 32 * LD + 16 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+          for (int pp = 0; pp < 4; ++pp) {
+            const float ge[4] = {ga[pp].x, ga[pp].y, ga[pp].z, ga[pp].w};
+            wacc[pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                ge[e], xe[e], wacc[pp], 0, 0, 0);
+          }
+        }
       }
     }
   }
@@ -756,7 +832,7 @@ std::vector<at::Tensor> proj_head_bwd_fused(const at::Tensor& gy,
     constexpr int IT = 20, MT = 128, O2T = decltype(o2t)::value;
     constexpr int TS = 64, LD = TS + 4;
     // the kernel's layout order: gzt [MT][LD], xt [IT][LD], gyt [O2T][TS],
-    // W3l [MT*IT], b3l [MT], W4l [O2T*MT], gb3s [MT], gW4s [O2T*MT]
+    // W3f + W3g [MT*IT], b3l [MT], W4l [O2T*MT], gb3s [MT], gW4s [O2T*MT]
     constexpr size_t smem = sizeof(float) *
         (MT * LD + IT * LD + O2T * TS + MT * IT + MT + O2T * MT + MT + O2T * MT);
     hipLaunchKernelGGL(
