@@ -160,7 +160,7 @@ def main():
 
 
 if __name__ == "__main__":
-    if not {"--dft", "--lift", "--wide"} & set(sys.argv):
+    if not {"--dft", "--lift", "--wide", "--wide-epilogue"} & set(sys.argv):
         main()
 
 
@@ -369,3 +369,71 @@ def wide_bench():
 
 if "__main__" == __name__ and "--wide" in sys.argv:
     wide_bench()
+
+
+def wide_epilogue_bench():
+    """Fused irfft epilogue at I = O = 64 (fp32) against the pairs it
+    replaces, alternating, five rounds, every round listed: a route wins when
+    its slowest round beats the other's fastest.  Shapes: the flagship trunk
+    (B = 1, S = 64^3 * 30, m = 8) and the width-64 Navier-Stokes trunk
+    ([10, 64, 64, 64, 40], m = 4).
+    Forward: irfft_linear_res_gelu_fwd (z stored) vs dft_pad_irfft +
+    wide_channel_mix (res + GELU, z stored).
+    Backward: rfft_adj_mix vs the transposed mix + dft_rfft_trunc_adj_acc,
+    the transposed mix being the MFMA one the model takes at this width and,
+    as a second partner, channel_mix_fwd_t."""
+    C = 64
+    e = torch.empty(0, device="cuda")
+    ms = lambda r: [round(t * 1e3, 3) for t in r]  # noqa: E731
+    for B, sp, N, m, iters in ((1, (64, 64, 64), 30, 8, 10),
+                               (10, (64, 64), 40, 4, 20)):
+        torch.manual_seed(0)
+        L = 1
+        for d in sp:
+            L *= d
+        S = L * N
+        tag = f"B={B} S={'x'.join(str(d) for d in sp)}x{N} m={m}"
+        act = B * C * S * 4
+        spec = B * C * L * m * 8
+        x = torch.randn(B, C, S, device="cuda")
+        W = torch.randn(C, C, device="cuda") / 8
+        Y = torch.randn(B, C, L, m, device="cuda", dtype=torch.complex64)
+
+        def fused_fwd():
+            return ext.irfft_linear_res_gelu_fwd(x, W, Y, N, True)
+
+        def pair_fwd():
+            r = ext.dft_pad_irfft(Y, 3, N, m).reshape(B, C, S)
+            return ext.wide_channel_mix(x, W, e, r, True, False, True)
+
+        tf, tp = _alternate([fused_fwd, pair_fwd], iters=iters, all_rounds=True)
+        report(f"fused fwd (x,Y,y,z) {tag}", sorted(tf)[2], 3 * act + spec)
+        report(f"irfft + wide mix fwd {tag}", sorted(tp)[2], 5 * act + spec)
+        print(f"  fused rounds ms {ms(tf)}  pair rounds ms {ms(tp)}  "
+              f"slowest fused < fastest pair: {max(tf) < min(tp)}")
+
+        def fused_adj():
+            return ext.rfft_adj_mix(x, W, Y, N)
+
+        def pair_adj():
+            g = ext.wide_channel_mix(x, W, e, e, False, True, False)[0]
+            return ext.dft_rfft_trunc_adj_acc(Y, 3, N, g.reshape(B, C, L, N))
+
+        def pair_adj_t():
+            g = ext.channel_mix_fwd_t(x, W)
+            return ext.dft_rfft_trunc_adj_acc(Y, 3, N, g.reshape(B, C, L, N))
+
+        tf, tp, tt = _alternate([fused_adj, pair_adj, pair_adj_t], iters=iters,
+                                all_rounds=True)
+        report(f"fused adjoint (gz,G,gx) {tag}", sorted(tf)[2], 2 * act + spec)
+        report(f"wide mix^T + rfft adj acc {tag}", sorted(tp)[2], 4 * act + spec)
+        report(f"channel_mix_fwd_t + rfft adj acc {tag}", sorted(tt)[2],
+               4 * act + spec)
+        print(f"  fused rounds ms {ms(tf)}  wide pair rounds ms {ms(tp)}  "
+              f"fwd_t pair rounds ms {ms(tt)}  slowest fused < fastest pair: "
+              f"{max(tf) < min(min(tp), min(tt))}")
+        del x, Y
+
+
+if "__main__" == __name__ and "--wide-epilogue" in sys.argv:
+    wide_epilogue_bench()

@@ -1014,11 +1014,13 @@ void launch_r2c(hipStream_t stream, const TI* in, T* out, const T* tw,
                 long lines, int N, int m, T scale, bool factors) {
   constexpr bool kBf16 = std::is_same_v<TI, unsigned short>;
   if constexpr (std::is_same_v<T, float>) {
-    // the ring is filled by whole 16-byte packets: aligned base, and at
-    // least one packet in the tensor for the last tile's clamp
+    // the ring is filled by whole 16-byte packets: aligned base, at least
+    // one packet in the tensor for the last tile's clamp, and a tensor that
+    // ends on a packet boundary (the clamp moves a packet that straddles the
+    // end back by a part of itself, so the last line would be staged shifted)
     constexpr int EPV = 16 / (int)sizeof(TI);
     if (N <= kMaxN && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
-        lines * N >= EPV) {
+        lines * N >= EPV && (lines * N) % EPV == 0) {
       // nt: the pinned length or 0; nmax: the longest N the instantiation
       // stages, which sets its DMA count
       auto glds = [&](auto nt, auto nmax, auto mc) {

@@ -290,9 +290,9 @@ std::vector<at::Tensor> irfft_linear_res_gelu_fwd(const at::Tensor& x,
   TORCH_CHECK((int)W.size(1) == I, "irfft_linear_res_gelu: W/I mismatch");
   TORCH_CHECK(Yt.size(0) == B && (int)Yt.size(1) == O && L * N == S,
               "irfft_linear_res_gelu: Yt shape mismatch");
-  TORCH_CHECK(I >= 1 && I <= 32 && O >= 1 && O <= 64 && N >= 1 && N <= 64 &&
+  TORCH_CHECK(I >= 1 && I <= 64 && O >= 1 && O <= 64 && N >= 1 && N <= 64 &&
               m >= 1 && m <= 32 && m <= N / 2 + 1,
-              "irfft_linear_res_gelu: needs I<=32, O<=64, N<=64, m<=min(32,N/2+1)");
+              "irfft_linear_res_gelu: needs I<=64, O<=64, N<=64, m<=min(32,N/2+1)");
 
   auto y = at::empty({B, O, S}, x.options());
   auto z = need_z ? at::empty({B, O, S}, x.options())
@@ -302,6 +302,11 @@ std::vector<at::Tensor> irfft_linear_res_gelu_fwd(const at::Tensor& x,
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   auto tw = dfno_twiddle_table(N, m, /*analysis=*/false, x.options());
   const float scale = (float)(1.0 / (double)N);
+  if (I > 32) {   // past the register-resident columns: the MFMA wide mix
+    wide_irfft_mix(x, W, Yt, tw, y, z, N, /*adj=*/false);
+    DFNO_CHECK_LAUNCH("irfft_linear_res_gelu");
+    return {y, z};
+  }
   float* yp = y.data_ptr<float>();
   float* zp = need_z ? z.data_ptr<float>() : yp;   // never stored through
   launch_irfft_mix<false>(x.data_ptr<float>(), W.data_ptr<float>(),
@@ -334,16 +339,23 @@ at::Tensor rfft_adj_mix(const at::Tensor& gz, const at::Tensor& W,
   TORCH_CHECK(G.size(0) == B && (int)G.size(1) == I && L * N == S,
               "rfft_adj_mix: G shape mismatch");
   // the roles swap against the forward mode: the mix's O channels are the
-  // register-resident ones (<= 32), its I channels the outputs (<= 64)
-  TORCH_CHECK(O >= 1 && O <= 32 && I >= 1 && I <= 64 && N >= 1 && N <= 64 &&
+  // contracted ones (register-resident up to 32, the MFMA wide mix past
+  // that), its I channels the outputs
+  TORCH_CHECK(O >= 1 && O <= 64 && I >= 1 && I <= 64 && N >= 1 && N <= 64 &&
               m >= 1 && m <= 32 && m <= N / 2 + 1,
-              "rfft_adj_mix: needs O<=32, I<=64, N<=64, m<=min(32,N/2+1)");
+              "rfft_adj_mix: needs O<=64, I<=64, N<=64, m<=min(32,N/2+1)");
 
   auto gx = at::empty({B, I, S}, gz.options());
   if (gz.numel() == 0) return gx;
 
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   auto tw = dfno_twiddle_table(N, m, /*analysis=*/false, gz.options());
+  if (O > 32) {
+    at::Tensor none = at::empty({0}, gz.options());
+    wide_irfft_mix(gz, W, G, tw, gx, none, N, /*adj=*/true);
+    DFNO_CHECK_LAUNCH("rfft_adj_mix");
+    return gx;
+  }
   float* gp = gx.data_ptr<float>();
   launch_irfft_mix<true>(gz.data_ptr<float>(), W.data_ptr<float>(),
                          reinterpret_cast<const float*>(G.data_ptr()),

@@ -51,6 +51,16 @@ std::vector<at::Tensor> irfft_linear_res_gelu_fwd(const at::Tensor& x,
 at::Tensor rfft_adj_mix(const at::Tensor& gz, const at::Tensor& W,
                         const at::Tensor& G, int64_t n);
 
+// the two entry points above at 33..64 register-side channels (fp32): the
+// MFMA wide mix of mix_wide.hip with the synthesis as its addend.  x [B,K,S],
+// Ys [B,M,L,m] complex64, tw = dfno_twiddle_table(N, m, false), y [B,M,S];
+// z [B,M,S] or empty (not stored).  adj = false: W [M,K], pad_irfft's
+// factors and GELU; adj = true: W [K,M] contracted over its rows, spectrum
+// as it is, plain sum.  The callers have checked dtypes and contiguity.
+void wide_irfft_mix(const at::Tensor& x, const at::Tensor& W, const at::Tensor& Ys,
+                    const at::Tensor& tw, at::Tensor& y, at::Tensor& z, int N,
+                    bool adj);
+
 // the cached host-built [N, m, 2] DFT twiddle table of dft.hip
 at::Tensor dfno_twiddle_table(int N, int m, bool analysis,
                               const at::TensorOptions& opt);

@@ -53,7 +53,12 @@ def fused_epilogue_enabled() -> bool:
 
 
 def fused_epilogue_ok(dtype, I: int, O: int, n_out: int, m: int) -> bool:
-    """Kernel range in terms of global configuration only."""
+    """Routed range in terms of global configuration only.  The entry point
+    also takes 33 to 64 input channels (the MFMA wide mix with the synthesis
+    as its addend, csrc/mix_wide.hip), but at the width-64 flagship shape
+    that kernel lost to ``pad_irfft`` + the wide mix, so wide blocks are not
+    routed to it (profiles/optimization_log.md, "Time-axis irfft in the wide
+    epilogue")."""
     return (dtype == torch.float32 and 1 <= I <= 32 and 1 <= O <= 64
             and 1 <= n_out <= 64 and 1 <= m <= min(32, n_out // 2 + 1))
 
@@ -65,8 +70,10 @@ def fused_rfft_adj_enabled() -> bool:
 
 
 def rfft_adj_mix_ok(dtype, I: int, O: int, n: int, m: int) -> bool:
-    """Range of the kernel's adjoint mode: the roles swap against the
-    forward, the mix's O channels are the register-resident ones."""
+    """Routed range of the adjoint mode: the roles swap against the
+    forward, the mix's O channels are the register-resident ones.  As in
+    the forward, the entry point takes up to 64 of them and, for the same
+    reason (same log entry), is not routed there."""
     return (dtype == torch.float32 and 1 <= O <= 32 and 1 <= I <= 64
             and 1 <= n <= 64 and 1 <= m <= min(32, n // 2 + 1))
 
